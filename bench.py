@@ -2,6 +2,10 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n-keys 1e9] [--n-seq 100000]
         (N > 1 without torchrun: bench.py starts the N ranks itself, one per GPU)
+        builds the image, warms up, times K steps and prints the result line
+    python bench.py ... --dump-outputs DIR   the last timed step's results as DIR/<name>.npy
+    python bench.py ... --full   also the canary, the kernel times and roofline, the parity
+        check, the host-path / lookup / pool legs, the microbenchmark and the CPU baseline
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], SURVEY §8(d) "C2"): per GPU, 100,000
@@ -483,6 +487,61 @@ def pool_lookup_leg(abi, synth, images, spec, pin, off, params, n_fam=100000):
     return out
 
 
+DUMP_SEQS = 4096        # sequences of the seeded sample whose rows are written
+DUMP_SEED = 0x6b6778    # fixed: the same sequences in every run of the same arguments
+DUMP_CAP = 64 << 20     # bytes, all files together
+
+
+def _as_float(a: np.ndarray) -> np.ndarray:
+    """a as float32 where that is exact for its type (float32, <= 16-bit
+    integers), else float64 (32-bit integers; the k-mer keys are < 20^8)."""
+    exact32 = (a.dtype.kind == "f" and a.dtype.itemsize <= 4) or (a.dtype.kind in "iu" and a.dtype.itemsize <= 2)
+    return np.ascontiguousarray(a, dtype=np.float32 if exact32 else np.float64)
+
+
+def dump_arrays(got, n_sample: int = DUMP_SEQS, cap: int = DUMP_CAP) -> dict:
+    """The arrays --dump-outputs writes, from the host CSR results of one step
+    (got: hit_offsets / hits, call_offsets / calls, best): every sequence's
+    hit and call count, and for a seeded sample of sequences (sample_seq,
+    ascending) their hits, calls and best calls, one array per record field,
+    rows in sequence order.  The sample is halved until all fit in cap."""
+    n = len(got.hit_offsets) - 1
+    ho = np.asarray(got.hit_offsets, np.int64)
+    co = np.asarray(got.call_offsets, np.int64)
+    out = {"hit_counts": np.diff(ho).astype(np.float32), "call_counts": np.diff(co).astype(np.float32)}
+    fixed = sum(a.nbytes for a in out.values())
+    k = min(n, n_sample)
+    while True:
+        sample = np.zeros(0, np.int64)
+        if k:
+            sample = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+        part = {"sample_seq": sample.astype(np.float64)}
+        for name, off, rows in (("hits", ho, got.hits), ("calls", co, got.calls)):
+            idx = np.concatenate([np.arange(off[s], off[s + 1]) for s in sample] + [np.zeros(0, np.int64)])
+            # the sample's own CSR: sequence sample_seq[i] owns rows [offsets[i], offsets[i + 1])
+            part[f"{name}_offsets"] = np.concatenate([[0], np.cumsum(off[sample + 1] - off[sample])]).astype(np.float64)
+            for f in rows.dtype.names:
+                part[f"{name}_{f}"] = _as_float(rows[f][idx])
+        if got.best is not None:
+            for f in got.best.dtype.names:
+                part[f"best_{f}"] = _as_float(got.best[f][sample])
+        if fixed + sum(a.nbytes for a in part.values()) <= cap or k == 0:
+            break
+        k //= 2
+    out.update(part)
+    return out
+
+
+def dump_outputs(path: str, got, rank: int = 0, world: int = 1) -> int:
+    """Write dump_arrays(got) as path/<name>.npy (rank r of a multi-rank job:
+    path/rank<r>_<name>.npy, its own shard); returns the bytes written."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dump_arrays(got)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -543,6 +602,16 @@ def main():
                     help="line-probe grid cap in workgroups per CU, waves striding over tiles (-1 = default)")
     ap.add_argument("--score-variant", type=int, default=0, help="0 = hybrid (default: lanes, long sequences on the wave scorer), 1 = wave-parallel, 2 = lanes only")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "probe_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the canary self-check, the probe / score kernel times and the "
+                         "roofline, the parity check against the oracle, the host-path, lookup and pool legs, the "
+                         "random-read microbenchmark and the CPU baseline (each with its --no-* switch); without "
+                         "it a run builds the image, settles the line index, warms up, times --steps steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (the host CSR results a caller collects: "
+                         "per-sequence counts, and the hits, calls and best calls of a fixed seeded sample of "
+                         "sequences) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
 
     from close_kmers_amd import shard
@@ -573,7 +642,7 @@ def main():
 
     d = shard.Dist()
     canary_recs = None
-    if not args.no_canary:
+    if args.full and not args.no_canary:
         canary_recs, canary_ok = canary_check(abi, synth, d, dev,
                                               args.line_index if args.image_layout == "packed" else 0)
         if not canary_ok:
@@ -692,11 +761,13 @@ def main():
         c.synchronize()
 
     # probe-kernel duration (HIP events on the context's stream), untimed
-    # pass, rotating over the batches like the timed steps
+    # pass, rotating over the batches like the timed steps (--full: the
+    # roofline's kernel time)
     probe_ms: list = []
-    for i in range(max(3, min(args.steps, 10))):
-        step(probe_ms, ctx, i)
-    ctx.synchronize()
+    if args.full:
+        for i in range(max(3, min(args.steps, 10))):
+            step(probe_ms, ctx, i)
+        ctx.synchronize()
 
     probe_ab = None
     if args.ab:
@@ -783,7 +854,7 @@ def main():
             f"without, {med['1']['median_step_ms']:.4f} with ({gain * 100:+.1f}%); probe "
             f"{med['0']['median_probe_ms']:.4f} / {med['1']['median_probe_ms']:.4f} ms; timed "
             f"{'with' if use_index else 'without'} the index")
-        if not use_index:  # the probe time under the timed configuration
+        if args.full and not use_index:  # the probe time under the timed configuration
             probe_ms.clear()
             for i in range(max(3, min(args.steps, 10))):
                 step(probe_ms, ctx, i)
@@ -820,21 +891,32 @@ def main():
     abi.check(L.kgx_memcpy_d2h(hc.ctypes.data, out.hit_count, hc.nbytes), "d2h")
     abi.check(L.kgx_memcpy_d2h(cc.ctypes.data, out.call_count, cc.nbytes), "d2h")
     total_hits = int(d.sum(float(hc.sum())))
+    probe_mean = float(np.mean(probe_ms)) if probe_ms else None  # None without --full
     mine = {"rank": d.rank, "device": dev, "ms_per_step": t_wall * 1e3 / args.steps,
-            "probe_ms": float(np.mean(probe_ms)), "n_seq": n, "hits": int(hc.sum())}
+            "probe_ms": probe_mean, "n_seq": n, "hits": int(hc.sum())}
     if canary_recs:
         c = canary_recs[d.rank]
         mine["canary"] = {"ok": c["ok"], "digest": c["digest"][:16], "hits": c["hits"], "calls": c["calls"]}
     per_rank = d.gather_objects(mine)
     log(f"[bench] rank {d.rank}: hits {int(hc.sum())} calls {int(cc.sum())} "
         f"(even-q mean {hc[::2].mean():.1f}, odd-q mean {hc[1::2].mean():.2f}); "
-        f"wall {t_wall * 1e3 / args.steps:.3f} ms/step ({len(ctxs)} worker contexts, {len(batches)} batches), "
-        f"probe {np.mean(probe_ms):.3f} ms")
+        f"wall {t_wall * 1e3 / args.steps:.3f} ms/step ({len(ctxs)} worker contexts, {len(batches)} batches)"
+        + (f", probe {probe_mean:.3f} ms" if probe_ms else ""))
+
+    # --dump-outputs: the last timed step's results, collected from the
+    # context that ran it before any later pass reuses its buffers
+    if args.dump_outputs:
+        t0 = time.time()
+        r = abi.Result()
+        abi.check(L.kgx_device_batch_collect(last.handle, want, ctypes.byref(r)), "collect")
+        nb = dump_outputs(args.dump_outputs, abi.BatchResult(r, want, copy=False), d.rank, d.world)
+        log(f"[bench] rank {d.rank}: outputs of timed step {args.steps - 1} (batch "
+            f"{(args.steps - 1) % len(batches)}) written, {nb / 1e6:.1f} MB in {time.time() - t0:.1f}s")
 
     # the timed configuration's results of batch 0, for the full-batch check
     # against the oracle below (rank 0)
     got0 = res0 = off0 = None
-    if d.rank == 0 and not args.no_parity:
+    if d.rank == 0 and args.full and not args.no_parity:
         step(None, ctx, 0)
         r = abi.Result()
         abi.check(L.kgx_device_batch_collect(ctx.handle, want, ctypes.byref(r)), "collect")
@@ -872,7 +954,7 @@ def main():
     # H2D residues, plan/probe/score, gather, D2H hits + calls) -- reported
     # beside `value`, never as it
     host_path = None
-    if d.rank == 0 and not args.no_host_path:
+    if d.rank == 0 and args.full and not args.no_host_path:
         d_res, d_off = batches[0]
         res_h = np.empty(n_res, np.uint8)
         off_h = np.empty(n + 1, np.uint64)
@@ -931,7 +1013,7 @@ def main():
             f"{n_res / t_x:.3e} with kgx_hit ({t_x * 1e3:.2f} ms); profiles {profiles}")
 
     host_path_lookup = None
-    if d.rank == 0 and not args.no_lookup:
+    if d.rank == 0 and args.full and not args.no_lookup:
         d_res, d_off = batches[0]
         res_h = np.empty(n_res, np.uint8)
         off_h = np.empty(n + 1, np.uint64)
@@ -940,7 +1022,7 @@ def main():
         host_path_lookup = host_path_lookup_leg(abi, synth, img, spec, dev, res_h, off_h, params, args.families)
 
     pool_e2e = pool_lookup = None
-    if d.rank == 0 and not (args.no_pool and args.no_pool_lookup):
+    if d.rank == 0 and args.full and not (args.no_pool and args.no_pool_lookup):
         # one replica per rank's device (the other ranks released theirs
         # above): the N-GPU run measures C5 over N devices
         pdevs = pool_devices(dev, n_dev, d.world)
@@ -962,7 +1044,7 @@ def main():
         del pin
 
     ceiling = None
-    if d.rank == 0 and not args.no_microbench:
+    if d.rank == 0 and args.full and not args.no_microbench:
         ceiling = {}
         n_reads = int(min(n, 100000) * max(0, Ls - 8) * 1.4)
         for mode, name, useful in ((0, "bucket24", 24), (1, "key8", 8), (2, "sector64", 64),
@@ -983,7 +1065,7 @@ def main():
     # the CPU port is timed at N=1 only (one host, one baseline; at N>1 the
     # other ranks would wait on rank 0's host copy of the image); the parity
     # check of batch 0 runs on rank 0 at every N
-    want_cpu = d.rank == 0 and d.world == 1 and not args.no_cpu_baseline
+    want_cpu = d.rank == 0 and d.world == 1 and args.full and not args.no_cpu_baseline
     if got0 is not None or want_cpu:
         import oracle
         oracle.build(ref=False)
@@ -1018,10 +1100,10 @@ def main():
         windows_per_launch = n * max(0, Ls - 8)  # x_permille = 0: every window is probed
         pbar = cpu["pbar"] if cpu else None
         pbar_source = "measured (CPU baseline leg, this run)" if pbar is not None else None
-        probe_s = float(np.mean(probe_ms)) / 1e3
+        probe_s = float(np.mean(probe_ms)) / 1e3 if probe_ms else None  # event-timed with --full
         traffic = None
         traffic_source = None
-        if os.path.exists(args.traffic_json):
+        if args.full and os.path.exists(args.traffic_json):
             try:
                 tj = json.load(open(args.traffic_json))
                 if (tj.get("n_keys") == n_keys and tj.get("keys_stored") == stored and tj.get("n_seq") == n
@@ -1042,7 +1124,7 @@ def main():
             pbar = 0.5 * (1 + 1 / (1 - a) ** 2)
             pbar_source = "analytic: linear probing, unsuccessful search (upper bound)"
         alg_bytes = windows_per_launch * (24.0 * pbar + 1.0)
-        achieved = alg_bytes / probe_s
+        achieved = alg_bytes / probe_s if probe_s else None
         residues_per_step_job = n_global * Ls  # every rank's shard of every step
         value = residues_per_step_job * args.steps / t_max
         if args.strong:
@@ -1087,7 +1169,7 @@ def main():
                             "check": "every rank's canary digest == the CPU oracle's (tests/golden/canary)"}
                            if canary_recs else None),
             },
-            "roofline": {
+            "roofline": None if not args.full else {
                 "bound": "hbm",
                 "achieved": achieved / 1e9,
                 "peak": HBM_PEAK / 1e9,

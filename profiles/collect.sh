@@ -21,17 +21,17 @@ cd /tmp && export TMPDIR=/tmp
 # (libkgx.so is built beforehand in the container and travels with the tree)
 echo "[collect] kernel trace" >&2
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt \
-    -- python3 "$R/bench.py" --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 20 > "$OUT/kt_bench.json" 2> "$OUT/kt_bench.err"
+    -- python3 "$R/bench.py" --full --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 20 > "$OUT/kt_bench.json" 2> "$OUT/kt_bench.err"
 echo "[collect] pmc FETCH_SIZE" >&2
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc \
-    -- python3 "$R/bench.py" --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 3 --warmup 1 > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
+    -- python3 "$R/bench.py" --full --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 3 --warmup 1 > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
 echo "[collect] pmc WRITE_SIZE" >&2
 timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc \
-    -- python3 "$R/bench.py" --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 3 --warmup 1 > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
+    -- python3 "$R/bench.py" --full --no-cpu-baseline --no-host-path --no-lookup --no-pool --no-pool-lookup --no-parity --line-index-ab 0 --pipeline 1 --steps 3 --warmup 1 > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
 python3 "$R/profiles/traffic.py" "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/pmc_fetch.json" > "$OUT/probe_traffic.json"
 cp "$OUT/probe_traffic.json" "$R/profiles/probe_traffic.json"
 echo "[collect] bench" >&2
-timeout -k 10 900 python3 "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 900 python3 "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[collect] done" >&2
 # the measured P (mean buckets per window, from the bench's CPU-baseline leg) goes with the traffic
 python3 - "$OUT/bench.json" "$R/profiles/probe_traffic.json" "$TAG" <<'PY'

@@ -257,3 +257,61 @@ def test_hbm_budget(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.hbm_check(abi, [0, 2], 180e9, "an image replica")
     assert "device 2: 100.0 GB of 288.0 GB HBM free, but an image replica needs 180.0 GB" in str(e.value)
+
+
+def _csr_result(n, seed=1, best=True):
+    """A host CSR result shaped like abi.BatchResult (the ABI's record types)."""
+    from close_kmers_amd import abi
+    rng = np.random.default_rng(seed)
+    ho = np.concatenate([[0], np.cumsum(rng.integers(0, 293, n))]).astype(np.uint64)
+    co = np.concatenate([[0], np.cumsum(rng.integers(0, 3, n))]).astype(np.uint64)
+    hits = np.zeros(int(ho[-1]), abi.HIT_DTYPE)
+    hits["which_kmer"] = rng.integers(0, 20 ** 8, len(hits))
+    hits["function_index"] = rng.integers(-1, 2 ** 31 - 1, len(hits))
+    hits["function_wt"] = rng.random(len(hits), np.float32)
+    hits["seq"] = np.repeat(np.arange(n), np.diff(ho).astype(np.int64))
+    calls = np.zeros(int(co[-1]), abi.CALL_DTYPE)
+    calls["start"] = np.arange(len(calls))
+    b = np.zeros(n, abi.BEST_DTYPE)
+    b["fi0"] = np.arange(n)
+    return types.SimpleNamespace(hit_offsets=ho, hits=hits, call_offsets=co, calls=calls, best=b if best else None)
+
+
+def test_dump_arrays_sample_is_fixed_exact_and_bounded():
+    """--dump-outputs: float32 / float64 arrays only, exact for every record
+    field, the same seeded sample of sequences on every call, the sample's
+    rows those sequences' own, and all of it within the byte cap."""
+    from close_kmers_amd import abi
+    got = _csr_result(6000)
+    a, b = bench.dump_arrays(got), bench.dump_arrays(got)
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_CAP
+    assert {f"hits_{f}" for f in abi.HIT_DTYPE.names} | {f"calls_{f}" for f in abi.CALL_DTYPE.names} \
+        | {f"best_{f}" for f in abi.BEST_DTYPE.names} <= set(a)
+    assert np.array_equal(a["hit_counts"], np.diff(got.hit_offsets.astype(np.int64)))
+    assert np.array_equal(a["call_counts"], np.diff(got.call_offsets.astype(np.int64)))
+    s = a["sample_seq"].astype(np.int64)
+    assert len(s) == bench.DUMP_SEQS == len(set(s.tolist())) and (np.diff(s) > 0).all() and s.max() < 6000
+    assert np.array_equal(np.diff(a["hits_offsets"]), a["hit_counts"][s])
+    assert np.array_equal(a["hits_seq"], np.repeat(s, a["hit_counts"][s].astype(np.int64)))
+    rows = np.concatenate([np.arange(got.hit_offsets[q], got.hit_offsets[q + 1], dtype=np.int64) for q in s])
+    for f in abi.HIT_DTYPE.names:  # no value changed by the conversion
+        assert np.array_equal(a[f"hits_{f}"].astype(abi.HIT_DTYPE[f]), got.hits[f][rows]), f
+    assert a["hits_which_kmer"].dtype == np.float64 and a["hits_function_wt"].dtype == np.float32
+    assert np.array_equal(a["best_fi0"], s)
+
+
+def test_dump_arrays_halves_the_sample_to_fit_and_writes_npy(tmp_path):
+    got = _csr_result(3000, best=False)
+    full = bench.dump_arrays(got, n_sample=2048)
+    cap = sum(v.nbytes for v in full.values()) - 1
+    a = bench.dump_arrays(got, n_sample=2048, cap=cap)
+    assert len(a["sample_seq"]) == 1024 and sum(v.nbytes for v in a.values()) <= cap
+    assert not any(k.startswith("best_") for k in a)
+    nb = bench.dump_outputs(str(tmp_path / "out"), got, rank=1, world=2)
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files and all(f.startswith("rank1_") and f.endswith(".npy") for f in files)
+    assert nb == sum(np.load(tmp_path / "out" / f).nbytes for f in files)
+    bench.dump_outputs(str(tmp_path / "one"), got)
+    assert np.array_equal(np.load(tmp_path / "one" / "hit_counts.npy"), full["hit_counts"])

@@ -10,12 +10,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-ranks}
 mkdir -p "$OUT"
 cd "$R"
-KGX_BENCH_DEVICE=0 timeout -k 10 300 python3 bench.py --gpus 2 --n-keys 1e8 --steps 20 --no-cpu-baseline \
+KGX_BENCH_DEVICE=0 timeout -k 10 300 python3 bench.py --full --gpus 2 --n-keys 1e8 --steps 20 --no-cpu-baseline \
     > "$OUT/bench2.json" 2> "$OUT/bench2.err" || { echo "[rehearse] weak failed: $?" >&2; exit 1; }
-KGX_BENCH_DEVICE=0 timeout -k 10 300 python3 bench.py --gpus 2 --n-keys 1e8 --strong --steps 20 \
+KGX_BENCH_DEVICE=0 timeout -k 10 300 python3 bench.py --full --gpus 2 --n-keys 1e8 --strong --steps 20 \
     --no-cpu-baseline > "$OUT/bench2_strong.json" 2> "$OUT/bench2_strong.err" \
     || { echo "[rehearse] strong failed: $?" >&2; exit 1; }
-timeout -k 10 120 python3 bench.py --gpus 2 --n-keys 1e8 --steps 5 --no-cpu-baseline \
+timeout -k 10 120 python3 bench.py --full --gpus 2 --n-keys 1e8 --steps 5 --no-cpu-baseline \
     > "$OUT/bench2_nodev.json" 2> "$OUT/bench2_nodev.err"
 rc=$?
 echo "[rehearse] --gpus 2 without the pin: rc $rc" >&2
