@@ -1068,7 +1068,7 @@ int fq_fragments_enqueue(kgx_ctx *c, const uint8_t *d_bases, const uint64_t *d_r
                          uint64_t n_bases, uint64_t bound)
 {
     /* fragments as anchors into the bases (no residues) when asked and the probe can take them */
-    const bool desc = !c->fq_residues && probe_takes_dna(c);
+    const bool desc = !c->opt.fq_residues && probe_takes_dna(c);
     hipStream_t st = c->stream;
     const uint64_t n_rf = (uint64_t)n_reads * 6;
     const uint64_t max_res = 2 * n_bases, max_frag = max_res / MIN_FRAGMENT + 1;
@@ -1101,7 +1101,7 @@ int fq_fragments_enqueue(kgx_ctx *c, const uint8_t *d_bases, const uint64_t *d_r
     ulonglong2 *tile_base = tile_sum + (n_tiles + 1);
     uint64_t *totals = reinterpret_cast<uint64_t *>(tile_base + (n_tiles + 1));
     void *scan_tmp = ws + ((((rc_bytes + 15) & ~15ull) + 2 * ts_bytes + 16 + 255) & ~255ull);
-    if (n_reads && desc && c->fq_fused && max_res < (1ull << 31)) {
+    if (n_reads && desc && c->opt.fq_fused && max_res < (1ull << 31)) {
         /* one pass: count + look-back scan + anchors */
         const uint32_t grid = (uint32_t)((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG);
         const size_t cap0 = c->fq_look.cap;
@@ -1124,7 +1124,7 @@ int fq_fragments_enqueue(kgx_ctx *c, const uint8_t *d_bases, const uint64_t *d_r
         hipLaunchKernelGGL(fq_count_lane_kernel<true>, dim3((uint32_t)((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG)),
                            dim3(256), 0, st, d_bases, d_read_off, n_reads, read_counts, tile_sum, (uint32_t)n_tiles,
                            c->fq_nfrag.as<uint32_t>(), c->fq_nres.as<uint32_t>());
-    else if (n_reads && c->fq_count)
+    else if (n_reads && c->opt.fq_count)
         hipLaunchKernelGGL(fq_count_lane_kernel<false>, dim3((uint32_t)((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG)),
                            dim3(256), 0, st, d_bases, d_read_off, n_reads, read_counts, tile_sum, (uint32_t)n_tiles,
                            nullptr, nullptr);

@@ -138,8 +138,6 @@ __host__ __device__ inline uint64_t filter_bits(uint64_t h)
 /* floor((2^64-1)/n): x % n = x - umulhi(x, m)*n, corrected once (x < 2^35). */
 inline uint64_t mod_magic(uint64_t n) { return n ? (~0ULL) / n : 0; }
 
-inline bool probe_j_supported(int j) { return (j >= 1 && j <= 5) || j == 8; }
-
 /* launchers; all asynchronous on `stream` */
 size_t plan_workspace_bytes(uint32_t n_seq);
 /* status[0] = 1 when the offsets are not monotone or span more than

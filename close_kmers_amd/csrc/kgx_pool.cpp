@@ -309,8 +309,8 @@ int kgx_pool_create(kgx_image *const *images, uint32_t n_images, uint32_t n_ctx,
      * slower than 2 contexts, r4x_bench_pool) */
     const unsigned cpus = host_cpu_budget();
     for (kgx_ctx *c : p->ctxs) {
-        c->stage_threads = (int)std::max(1u, std::min<unsigned>((unsigned)c->stage_threads, cpus / n_ctx));
-        c->host_threads = (int)std::max(1u, std::min<unsigned>((unsigned)c->host_threads, cpus / n_ctx));
+        c->opt.stage_threads = (int)std::max(1u, std::min<unsigned>((unsigned)c->opt.stage_threads, cpus / n_ctx));
+        c->opt.host_threads = (int)std::max(1u, std::min<unsigned>((unsigned)c->opt.host_threads, cpus / n_ctx));
     }
     p->expand_threads = std::max(1u, std::min(p->expand_threads, cpus));
     if (const char *e = std::getenv("KGX_POOL_PER_DEVICE"))
@@ -765,17 +765,9 @@ int kgx_pool_lookup(kgx_pool *p, kgx_kmap *const *maps, uint32_t n_maps, int mod
      * behind shard 2's upload).  Each shard's rollup follows its pass on the
      * context's stream (sized by the context's previous rollup); the collects
      * and the rollups' checks then run on the pool's threads. */
-    while (p->up_done.size() < K) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        p->up_done.push_back(e);
-    }
-    for (auto *v : {&p->pass_done, &p->roll_done})
-        while (v->size() < K) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            v->push_back(e);
-        }
+    for (auto *v : {&p->up_done, &p->pass_done, &p->roll_done})
+        if (int erc = ensure_events(*v, K))
+            return erc;
     for (uint32_t i = 0; i < K; i++) {
         kgx_ctx *c = p->ctxs[run[i]];
         const int dev = kgx_image_device(c->img);
@@ -795,9 +787,9 @@ int kgx_pool_lookup(kgx_pool *p, kgx_kmap *const *maps, uint32_t n_maps, int mod
         /* a shard's sequences on the host path's scorer (option
          * host_score_variant: the wave scorer; the lane scorer's longest
          * chain sets a shard's score time whatever its size) */
-        const int sv = c->score_variant;
-        if (c->host_score_variant >= 0)
-            c->score_variant = c->host_score_variant;
+        const int sv = c->opt.score_variant;
+        if (c->opt.host_score_variant >= 0)
+            c->opt.score_variant = c->opt.host_score_variant;
         /* the pass (and its counts' copy) on the device's pass stream, the
          * rollup on its rollup stream behind it; the context's own stream
          * gets nothing (a wait on it could sit in the pass stream's queue) */
@@ -809,7 +801,7 @@ int kgx_pool_lookup(kgx_pool *p, kgx_kmap *const *maps, uint32_t n_maps, int mod
             p->lookup_stage.reset(new HostPool(std::max(1u, host_cpu_budget())));
         rcs[i] = one_pass_enqueue(c, params, residues, seq_offsets + cuts[i], cuts[i + 1] - cuts[i], want,
                                   p->up_stream[(size_t)dev], p->up_done[i], p->lookup_stage.get());
-        c->score_variant = sv;
+        c->opt.score_variant = sv;
         c->score_stream = nullptr;
         c->stream = ss; /* the counts and best calls behind the score */
         if (!rcs[i])

@@ -1,6 +1,7 @@
 /*
  * kgx_rt.h -- host runtime internals shared by the C ABI translation units
- * (kgx_runtime.cpp: images, contexts, batches; kgx_tables.cpp: k-mer -> id
+ * (kgx_runtime.cpp: images, contexts, stages; kgx_host_batch.cpp: host-buffer
+ * batches; kgx_pool.cpp: context pools; kgx_tables.hip: k-mer -> id
  * tables and /matrix pair counting).  Not part of the public ABI.
  */
 #ifndef KGX_RT_H
@@ -10,7 +11,10 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -21,6 +25,7 @@
 #include <vector>
 
 #include "kgx_internal.h"
+#include "kgx_options.h"
 
 namespace kgx {
 
@@ -34,6 +39,17 @@ bool is_gfx950(int dev);
         if (e_ != hipSuccess)                                                                \
             return ::kgx::fail(KGX_EDEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
+
+/* v holds at least n events (created with flags) */
+inline int ensure_events(std::vector<hipEvent_t> &v, size_t n, unsigned flags = hipEventDisableTiming)
+{
+    while (v.size() < n) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        v.push_back(e);
+    }
+    return KGX_OK;
+}
 
 /* How a thread waits for its own stream (kgx_set_host_wait): KGX_WAIT_SPIN
  * (hipStreamSynchronize: the runtime polls), KGX_WAIT_SLEEP (hipStreamQuery
@@ -382,8 +398,6 @@ struct kgx_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t probe_done = nullptr; /* recorded after each of this context's probes */
-    int probe_serialize = 1;          /* option "probe_serialize" */
-    int probe_stream = 0;             /* chained probes on the image's probe stream (option "probe_stream") */
     hipEvent_t probe_ready = nullptr; /* this context's inputs are ready for its probe */
     /* a pool's /lookup: the stream the pass's score runs on after its probe
      * (null: the context's stream), behind score_gate recorded after the probe */
@@ -396,7 +410,6 @@ struct kgx_ctx {
     kgx::DevBuf plan_status;
     /* the one-launch plan's look-back states (zero between launches) */
     kgx::DevBuf plan_look;
-    int plan_fused = 0; /* option "plan_fused": 0 = three kernels, 1 = one look-back launch, 2 = one workgroup */
     kgx::PinnedVec<uint32_t> h_plan_status;
     /* current plan */
     uint32_t n_seq = 0;
@@ -430,24 +443,7 @@ struct kgx_ctx {
     kgx::PinnedVec<uint32_t> h_fqc_n, h_fqc_reads, h_fqc_fc, h_fqc_len;
     kgx::PinnedVec<uint64_t> h_fqc_tot, h_fqc_fo, h_fqc_coff;
     kgx::PinnedVec<kgx_call> h_fqc_calls;
-    /* tuning options */
-    int probe_variant = kgx::PROBE_AUTO;
-    int probe_j = kgx::PROBE_J_DEFAULT;
-    int probe_lds_kb = 0;  /* LDS reserved per probe workgroup, caps its occupancy (option "probe_lds_kb") */
-    int probe_persist = 0; /* line probe grid cap in workgroups per CU, waves stride over tiles (option "probe_persist") */
-    int fq_residues = 1;   /* 1: kgx_fq_fragments writes residues; 0: anchors (kgx_fq_run_device) */
-    int fq_count = 1;      /* fq count pass: 1 = lane-per-read stop scan, 0 = wave-per-read translation */
-    int fq_probe_j = 1;    /* tile of the DNA probe (fragments as anchors), 64 x J windows; 0 = probe_j */
-    int fq_plan = 1;       /* 1: this context's fragments are planned elementwise (fq_plan_kernel); 0: launch_plan */
-    int fq_fused = 1;      /* anchors: count + scan + emit in one look-back pass (fq_anchor_fused_kernel); 0: four launches */
-    int score_variant = 0; /* 0 = hybrid, 1 = wave-parallel, 2 = lane only (option "score_variant", kgx_internal.h) */
-    int score_wave_tiles = 16; /* probe tiles of windows per scorer wave (option "score_wave_tiles") */
-    int probe_filter = 1; /* use the image's presence filter when it has one */
-    int use_line_index = 1; /* option "line_index": 0 = probe the reference slots even when the image has a line index */
-    int probe_nt = 0;       /* option "probe_nt": 1 = the line probe's hit stores non-temporal */
-    uint64_t microbench_span = 0; /* bytes of the table the random-read ceiling covers; 0 = all */
-    int microbench_ilp = 8;       /* independent reads in flight per lane */
-    int microbench_wgs = 8;       /* 256-thread workgroups per CU */
+    kgx::CtxOptions opt; /* the tuning options (kgx_ctx_set_option; kgx_options.h) */
     /* host results */
     std::vector<uint64_t> h_hoff, h_coff, h_ooff;
     kgx::PinnedVec<kgx_hit> h_hits;
@@ -459,25 +455,12 @@ struct kgx_ctx {
     bool have_otus = false;
     kgx::PinnedVec<uint32_t> h_hcount, h_ccount;
     kgx::PinnedVec<char> h_res;
-    /* host-buffer batches in chunks (option "host_chunks"): chunks alternate
-     * between this context and a twin over the same image, so one chunk's
-     * gather + D2H overlaps the next chunk's H2D + kernels */
-    int host_chunks = 6;
-    int host_copy = 1; /* chunk D2H: 0 = DMA (hipMemcpyAsync), 1 = device stores into mapped memory */
-    int host_copy_blocks = 64; /* workgroups of the store copy (option "host_copy_blocks") */
+    /* host-buffer batches in chunks (option "host_chunks"): the other context
+     * the chunks alternate with */
     kgx_ctx *twin = nullptr;
     kgx::PinnedVec<uint64_t> h_off_stage, h_dense_hoff, h_dense_coff, h_dense_ooff, h_nwin;
-    /* compact chunk D2H (option "host_hits16", PACKED16 images): a chunk's
-     * hits cross PCIe as their 16-byte table records plus the chunk's hit
-     * mask, and host threads expand them into kgx_hit (position = mask bit)
-     * while the next chunk streams */
-    int host_hits16 = 1;
-    int host_threads = 12; /* expansion threads (option "host_threads") */
-    std::unique_ptr<kgx::HostPool> pool;
-    /* chunk staging (pageable caller buffer -> pinned) in parts on
-     * stage_threads threads (option "stage_threads", 1 = the calling thread) */
-    int stage_threads = 8; /* option "stage_threads": r4ag, 3.57-3.65 vs 3.71-3.90 ms per batch with 4 */
-    std::unique_ptr<kgx::HostPool> stage_pool;
+    std::unique_ptr<kgx::HostPool> pool;       /* compact chunk D2H: the expansion threads (option "host_threads") */
+    std::unique_ptr<kgx::HostPool> stage_pool; /* chunk staging threads (option "stage_threads") */
     kgx::PinnedVec<uint4> h_hits16;
     kgx::PinnedVec<uint64_t> h_mask;
     std::vector<uint64_t> h_wstart;     /* chunk-relative first window of each sequence */
@@ -485,32 +468,12 @@ struct kgx_ctx {
     std::vector<hipEvent_t> chunk_counts; /* per chunk: its counts are on the host */
     std::vector<hipEvent_t> chunk_gathered; /* per chunk: its dense buffers are complete */
     hipStream_t copy_stream = nullptr; /* bulk chunk D2H, apart from the contexts' kernels */
-    /* streamed schedule, option "host_upload_stream" 1: every chunk's residues
-     * and offsets go up on a stream of their own into a region of the
-     * batch's own (up_res / up_off), as soon as they are staged, instead of
-     * behind the previous chunk's kernels on the context's stream.  Off by
-     * default: with the runtime's 4 hardware queues per process the upload
-     * stream shares one with a stream that waits on events, and measured no
-     * faster (r4l/r4m: 3.66-4.21 vs 3.76-4.09 ms per 30M-residue batch; with
-     * 16 queues the uploads do run early, 3.60-3.90 ms) */
-    int host_upload_stream = 0;
-    int host_score_variant = 1; /* streamed chunks' scorer (option "host_score_variant"; -1: score_variant) */
-    hipStream_t up_stream = nullptr;
+    hipStream_t up_stream = nullptr; /* streamed schedule, option "host_upload_stream": the chunks' uploads */
     kgx::DevBuf up_res, up_off;
     kgx::DevBuf dense_mask, dense_best; /* a chunk's mask / best calls for its bulk copy */
-    /* streamed schedule (option "host_stream", compact records only): device
-     * CSR offsets, bulk copies sized on the device into host regions sized
-     * from the rates below (records per window seen so far, x 1.25) */
-    int host_stream_chunks = 1;
-    int host_taper = 1; /* first and last chunk half-size (option "host_taper") */
+    /* streamed schedule (option "host_stream"): records per window seen so far */
     double rate_hits = 0.35, rate_calls = 0.05, rate_otus = 0.05;
     uint64_t stream_fallbacks = 0; /* batches rerun exact after a region overflowed */
-    /* option "pinned_input" (default 1): a streamed host batch whose residues
-     * already sit in pinned memory (kgx_host_alloc, hipHostMalloc /
-     * hipHostRegister) goes to the device by DMA straight from the caller's
-     * buffer, with no staging copy on the host; a device scan flags NUL bytes
-     * (the host-side strlen cut, kguts.cc:792) and such a batch reruns staged */
-    int pinned_input = 1;
     bool one_pass_pinned = false; /* the enqueued one-pass batch reads caller-pinned residues */
     uint64_t pinned_batches = 0, nul_reruns = 0;
     uint32_t counts_enqueued = 0; /* want + 1 of an enqueued collect_counts_enqueue, else 0 */
@@ -519,31 +482,15 @@ struct kgx_ctx {
     kgx::DevBuf dense_counts, cscan_ws;
     kgx::PinnedVec<uint32_t> h_counts;
     kgx::PinnedVec<uint32_t> h_hits12; /* 12-B records (3 words per hit, no key) */
-    int host_rec12 = 1; /* streamed: 12-B records, key re-encoded on the host (option "host_rec12") */
-    int host_h2d_first = 1; /* streamed: chunk k's D2H waits for chunk k+1's H2D (option "host_h2d_first") */
-    /* streamed: every chunk staged into its own region of h_res_all / h_off_all
-     * (option "host_stage_all"), not into the context's h_res behind the H2D of
-     * the chunk two before */
-    int host_stage_all = 0; /* r4ak: 3.61-3.70 vs 3.49-3.73 ms per batch, no gain */
+    /* streamed, option "host_stage_all": every chunk's own staging region */
     kgx::PinnedVec<char> h_res_all;
-    /* streamed: chunk copies by DMA (hipMemcpyAsync of each region whole, at
-     * its host-sized room) instead of the counted device-store copy (option
-     * "host_stream_dma") */
-    int host_stream_dma = 0;
     kgx::PinnedVec<uint64_t> h_off_all;
-    /* small host batches (<= small_batch residues, option "small_batch", 0 =
-     * off): planned on the host, read by the device from the mapped staging
-     * blob, results stored into mapped memory: one host wait per batch */
-    int64_t small_batch = 1 << 21; /* 2M residues: a 1-MiB request body and then some */
-    int small_wave = 1; /* small batches: the wave scorer instead of the hybrid (option "small_wave") */
-    int small_wave_tiles = 1; /* small batches: probe tiles per scorer wave (option "small_wave_tiles") */
+    /* small host batches (option "small_batch") */
     kgx::PinnedVec<uint4> h_small; /* offsets | window bases | tile owners | status | residues */
     kgx::PinnedVec<uint32_t> h_done; /* the fused small gather's completion token */
     kgx::DevBuf small_blocks_done;    /* its workgroup counter (zero between launches) */
     /* one-launch small batches (option "small_fused"; kgx_fused.hip): mapped
      * window bases, per-sequence result regions, counts and tokens */
-    int small_fused = 0;
-    int fused_inline = 1; /* a tiny fused batch travels in the kernel arguments (option "fused_inline") */
     uint64_t fused_batches = 0, small_batches = 0; /* kgx_ctx_stat */
     kgx::PinnedVec<uint64_t> h_fwb;
     kgx::PinnedVec<kgx_hit> h_fhits;
@@ -551,10 +498,8 @@ struct kgx_ctx {
     kgx::PinnedVec<uint32_t> h_fcounts, h_fdone;
     kgx::PinnedVec<uint64_t> h_fdbg; /* KGX_FUSED_DEBUG phase stamps */
     uint32_t small_token = 0;
-    int host_nt = 1;    /* expansion with streaming stores (option "host_nt") */
     kgx::PinnedVec<kgx_call> h_calls_region;
     kgx::PinnedVec<kgx_otu> h_otus_region;
-    int counts_first = 1; /* chunk k's bulk D2H waits for chunk k+1's counts (option "counts_first") */
     /* compact results (kgx_process_batch_compact): the call leaves the hits as
      * records + mask; compact_segs say where each chunk's landed (element
      * offsets into h_hits12 / h_hits16 and h_mask, resolved to pointers once
@@ -567,7 +512,6 @@ struct kgx_ctx {
     std::vector<CompactSeg> compact_segs;
     std::vector<kgx_hit_chunk> compact_chunks;
     /* option "host_profile": per-chunk timing events and the last call's profile */
-    int host_profile = 0;
     std::vector<hipEvent_t> prof_ev; /* 4 per chunk: H2D start, H2D end, device end, gathered */
     std::vector<hipEvent_t> prof_done; /* per chunk: bulk copy done (timing events on the copy stream) */
     kgx_host_profile last_profile{};
@@ -576,14 +520,47 @@ struct kgx_ctx {
 };
 
 namespace kgx {
+static_assert(CtxOptions{}.probe_variant == PROBE_AUTO && CtxOptions{}.probe_j == PROBE_J_DEFAULT,
+              "kgx_options.h spells these two defaults as numbers");
 /* what c's probes read: the image's line index unless option "line_index" is 0 */
-inline bool ctx_lines(const kgx_ctx *c) { return c->img->d_lines && c->use_line_index; }
+inline bool ctx_lines(const kgx_ctx *c) { return c->img->d_lines && c->opt.line_index; }
 inline const void *ctx_probe_table(const kgx_ctx *c)
 {
     return ctx_lines(c) ? static_cast<const void *>(c->img->d_lines) : c->img->resident();
 }
 inline uint64_t ctx_probe_buckets(const kgx_ctx *c) { return ctx_lines(c) ? 4 * c->img->n_lines : c->img->num_sigs; }
 inline uint32_t ctx_home_shift(const kgx_ctx *c) { return ctx_lines(c) ? 2u : 0u; }
+/* a host batch's result: the context's host arrays */
+inline void fill_result(kgx_ctx *c, uint32_t n_seq, bool need_hits, bool want_best, uint64_t nwin, kgx_result *out)
+{
+    out->best = want_best ? c->h_best.data() : nullptr;
+    out->n_seq = n_seq;
+    out->hit_offsets = c->h_hoff.data();
+    out->hits = need_hits ? c->h_hits.data() : nullptr;
+    out->call_offsets = c->h_coff.data();
+    out->calls = c->h_calls.data();
+    out->otu_offsets = c->h_ooff.data();
+    out->otus = c->h_otus.data();
+    out->n_windows = nwin;
+}
+
+/* KGX_TIMING=1: phase wall times of the host-buffer path on stderr */
+struct PhaseTimer {
+    kgx_ctx *c;
+    bool on;
+    std::chrono::steady_clock::time_point t;
+    explicit PhaseTimer(kgx_ctx *ctx) : c(ctx), on(std::getenv("KGX_TIMING") != nullptr), t(std::chrono::steady_clock::now()) {}
+    void mark(const char *what)
+    {
+        if (!on)
+            return;
+        (void)hipStreamSynchronize(c->stream);
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[kgx] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
+
 /* one chunk of compact records -> kgx_hit for sequences [a, b) of it:
  * out[j - out_base] for CSR hit j (hoff: the batch's hit offsets);
  * kgx_hit.seq = s + seq_base; nt = streaming stores */

@@ -196,8 +196,8 @@ void serve_connection(KmerRequestRouter &router, int fd)
     const std::string resp = router.handle(req, &quit);
     const uint64_t t_send = clock_ns();
     write_all(fd, resp.data(), resp.size());
-    ::shutdown(fd, SHUT_WR);
-    ::close(fd);
+    /* counted before the client sees the end of the response: a
+     * /server_stats request that follows it finds this one in the totals */
     if (req.path != "/server_stats") {
         const uint64_t t_end = clock_ns();
         st.requests++;
@@ -207,6 +207,8 @@ void serve_connection(KmerRequestRouter &router, int fd)
         st.handle_ns += t_send - t_handle;
         st.send_ns += t_end - t_send;
     }
+    ::shutdown(fd, SHUT_WR);
+    ::close(fd);
     if (quit) {
         std::cerr << "stopping io service\n";
         g_stop = true;

@@ -864,6 +864,39 @@ def test_host_profile_reports_the_streamed_stages(small_world, gpu):
         ctx.set_option("host_chunks", 3)
 
 
+# kgx_ctx_set_option's 43 names and their defaults (tests/native/options_check.cpp has the ranges and texts)
+OPTION_DEFAULTS = {
+    "microbench_ilp": 8, "microbench_wgs": 8, "microbench_span": 0, "probe_filter": 1, "probe_variant": -1,
+    "plan_fused": 0, "probe_nt": 0, "line_index": 1, "probe_serialize": 1, "host_copy_blocks": 64, "host_copy": 1,
+    "host_hits16": 1, "stage_threads": 8, "host_score_variant": 1, "host_upload_stream": 0, "host_stream_dma": 0,
+    "pinned_input": 1, "host_stage_all": 0, "host_h2d_first": 1, "host_rec12": 1, "host_nt": 1, "host_taper": 1,
+    "host_stream": 1, "counts_first": 1, "host_threads": 12, "small_batch": 1 << 21, "probe_stream": 0,
+    "probe_persist": 0, "small_wave": 1, "host_profile": 0, "host_chunks": 6, "fq_count": 1, "fq_residues": 1,
+    "score_variant": 0, "probe_lds_kb": 0, "fused_inline": 1, "small_fused": 0, "small_wave_tiles": 1,
+    "score_wave_tiles": 16, "fq_fused": 1, "fq_plan": 1, "fq_probe_j": 1, "probe_j": 2,
+}
+
+
+def test_every_option_through_the_abi(small_world, oracle_lib, gpu):
+    """All 43 option names are taken at their defaults by a real context, a
+    value out of range and an unknown name are KGX_EINVAL with the recorded
+    text, and the context still computes the oracle's results afterwards."""
+    spec, table, img, _ = small_world
+    assert len(OPTION_DEFAULTS) == 43
+    set_option = gpu.lib().kgx_ctx_set_option
+    with gpu.Context(img) as ctx:
+        for name, value in OPTION_DEFAULTS.items():
+            assert set_option(ctx.handle, name.encode(), value) == 0, (name, gpu.last_error())
+        for name, value, text in (("host_chunks", 0, "host_chunks must be 1..64"),
+                                  ("probe_variant", 4, "probe_variant must be -1, 0, 1, 2 or 3"),
+                                  ("no_such_option", 1, "unknown option no_such_option")):
+            assert set_option(ctx.handle, name.encode(), value) == gpu.KGX_EINVAL, name
+            assert gpu.last_error() == text
+        res, off = synth.make_queries(spec, 200, x_permille=5)
+        got = ctx.process_batch(res, off)
+    assert_same(got, oracle_lib.process_batch(table, res, off), 200)
+
+
 # ---------------------------------------------------------------------------
 # find_best_call on the device (KGX_WANT_BEST, kgx_find_best_calls)
 
