@@ -193,6 +193,7 @@ SIGNATURES = {
     "kgx_image_set_layout": (_INT, [_P, _INT]),
     "kgx_image_set_line_index": (_INT, [_P, _U32]),
     "kgx_image_line_count": (_U64, [_P]),
+    "kgx_image_line_home": (_U32, [_P]),
     "kgx_image_set_filter": (_INT, [_P, _INT]),
     "kgx_image_download": (_INT, [_P, _P, _U64]),
     "kgx_ctx_create": (_INT, [_P, _PP]),
@@ -449,6 +450,11 @@ class Image:
     @property
     def line_count(self) -> int:
         return lib().kgx_image_line_count(self.handle)
+
+    @property
+    def line_home(self) -> int:
+        """the KGX_LINE_HOME mode the line index was built with (0 mod, 1 minimizer)"""
+        return lib().kgx_image_line_home(self.handle)
 
     def download(self) -> np.ndarray:
         t = np.empty(self.num_sigs, dtype=SIG_DTYPE)

@@ -5,6 +5,7 @@
 #define KGX_DEVICE_H
 
 #include "kgx_internal.h"
+#include "kgx_line_home.h" /* mod_by, line_home, home_bucket */
 
 namespace kgx {
 
@@ -29,15 +30,6 @@ __device__ __forceinline__ char code11_aa(uint32_t e)
 {
     const char *t = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF";
     return t[e & 63u];
-}
-
-/* x % n for x < 2^35, n >= 1, m = floor((2^64-1)/n): the quotient estimate
- * is exact or one short, so one conditional subtraction finishes it */
-__device__ __forceinline__ uint64_t mod_by(uint64_t x, uint64_t n, uint64_t m)
-{
-    uint64_t q = __umul64hi(x, m);
-    uint64_t r = x - q * n;
-    return r >= n ? r - n : r;
 }
 
 /* splitmix64 finaliser; rnd(seed, i) = mix64(seed ^ mix64(i)) (synth.py) */

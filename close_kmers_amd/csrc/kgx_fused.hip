@@ -42,8 +42,8 @@ struct FusedArgs {
     uint32_t n;
     uint32_t want;
     const uint4 *table; /* PACKED16 records in HBM */
-    uint64_t num_sigs, magic; /* buckets; magic of num_sigs >> hs */
-    uint32_t hs;              /* home = (key mod (num_sigs >> hs)) << hs (kgx_image_set_line_index) */
+    uint64_t num_sigs, magic; /* buckets; magic of num_sigs >> the home shift */
+    uint32_t hs;              /* home shift and mode: home_bucket (kgx_line_home.h) */
     kgx_params prm;
     kgx_hit *hits;    /* mapped: sequence s's hits from hits[wbase[s]] */
     kgx_call *calls;  /* mapped: sequence s's calls from calls[wbase[s]] */
@@ -171,7 +171,7 @@ __device__ __forceinline__ void fused_small_body(const FusedArgs &a, const IN &k
                 const uint32_t kb = ((c[4] * 20u + c[5]) * 20u + c[6]) * 20u + c[7];
                 k = (uint64_t)ka * 160000u + kb;
                 pd = cmax < 20u;
-                sl = pd ? mod_by(k, a.num_sigs >> a.hs, a.magic) << a.hs : 0;
+                sl = pd ? home_bucket(k, a.num_sigs, a.magic, a.hs) : 0;
             };
 #pragma unroll
             for (uint32_t j = 0; j < RB; j++) {
@@ -805,7 +805,7 @@ hipError_t launch_fused_small(const uint8_t *res, const uint64_t *off, const uin
     a.want = want;
     a.table = static_cast<const uint4 *>(packed_table);
     a.num_sigs = num_sigs;
-    a.magic = mod_magic(num_sigs >> hs);
+    a.magic = mod_magic(num_sigs >> home_shift_of(hs));
     a.hs = hs;
     a.prm = prm;
     a.hits = hits;
@@ -1017,13 +1017,14 @@ hipError_t launch_svc(const SvcSlotHdr *hdr, SvcSlotOut *out, SvcSlotDbg *dbg, c
     poll_chunks = std::min(poll_chunks, SVC_POLL_CHUNKS);
     if (slots == 0 || slots > SVC_MAX_SLOTS || num_sigs == 0 || !packed_table)
         return hipErrorInvalidValue;
+    const uint64_t magic = mod_magic(num_sigs >> home_shift_of(hs));
     if (quad_probe)
         hipLaunchKernelGGL(svc_kernel<true>, dim3(slots), dim3(256), 0, stream, hdr, out, dbg, res, hits, calls, otus,
-                           static_cast<const uint4 *>(packed_table), num_sigs, mod_magic(num_sigs >> hs), hs,
+                           static_cast<const uint4 *>(packed_table), num_sigs, magic, hs,
                            life_ticks, poll_chunks);
     else
         hipLaunchKernelGGL(svc_kernel<false>, dim3(slots), dim3(256), 0, stream, hdr, out, dbg, res, hits, calls,
-                           otus, static_cast<const uint4 *>(packed_table), num_sigs, mod_magic(num_sigs >> hs), hs,
+                           otus, static_cast<const uint4 *>(packed_table), num_sigs, magic, hs,
                            life_ticks, poll_chunks);
     return hipGetLastError();
 }

@@ -1,0 +1,93 @@
+/*
+ * kgx_line_home.h -- the home line of a key in the line index
+ * (kgx_image_set_line_index), one function for the builder and every probe.
+ * Plain C++ as well as HIP: tests/native/line_home_check.cpp runs it on the
+ * host.
+ *
+ * The index holds, once each, the records the reference's probe reaches
+ * first; any deterministic home followed by a linear probe to the key or to
+ * an empty bucket returns them, so the home is the index's own choice.
+ *
+ *   LINE_HOME_MOD        key mod n_lines.
+ *   LINE_HOME_MINIMIZER  a key is two overlapping 7-mers, A = key / 20 (its
+ *     first seven residues) and B = key mod 20^7 (its last seven); its home
+ *     is hashed from whichever of the two has the smaller hash.  Window i's B
+ *     is window i + 1's A, so two neighbouring windows of a sequence share
+ *     their home line whenever the 7-mer they share is the minimizer of both:
+ *     it has the smallest hash of three, probability 1/3, present or absent.
+ *     A 7-mer lies in two windows only, so no more than two in a row share.
+ */
+#ifndef KGX_LINE_HOME_H
+#define KGX_LINE_HOME_H
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define KGX_HD __host__ __device__ __forceinline__
+#else
+#define KGX_HD inline
+#endif
+
+namespace kgx {
+
+constexpr uint32_t LINE_HOME_MOD = 0, LINE_HOME_MINIMIZER = 1;
+
+/* What the probe launchers take as `home_shift`: bits 0-7 the shift hs (a
+ * key's home bucket is home(key) << hs over num_sigs >> hs homes: 0 the
+ * reference slots, 2 the 4-bucket lines of the index), bits 8 and up the
+ * LINE_HOME_* mode of the image's index (0 where hs is 0). */
+constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8;
+KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode) { return shift | mode << HOME_MODE_SHIFT; }
+KGX_HD uint32_t home_shift_of(uint32_t home) { return home & HOME_SHIFT_MASK; }
+
+/* x % n for x < 2^35, n >= 1, m = floor((2^64-1)/n): the quotient estimate
+ * is exact or one short, so one conditional subtraction finishes it */
+KGX_HD uint64_t mod_by(uint64_t x, uint64_t n, uint64_t m)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t q = __umul64hi(x, m);
+#else
+    const uint64_t q = (uint64_t)(((unsigned __int128)x * m) >> 64);
+#endif
+    const uint64_t r = x - q * n;
+    return r >= n ? r - n : r;
+}
+
+/* a 32-bit bijective mixer (two multiply-xorshift rounds); the added constant
+ * keeps 7-mer 0 from hashing to 0, the minimum */
+KGX_HD uint32_t mix32(uint32_t x)
+{
+    x += 0x9E3779B9u;
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
+/* the home line of `key` (<= 20^8) among n_lines, magic = mod_magic(n_lines) */
+KGX_HD uint64_t line_home(uint64_t key, uint64_t n_lines, uint64_t magic, uint32_t mode)
+{
+    if (mode == LINE_HOME_MOD)
+        return mod_by(key, n_lines, magic);
+    const uint32_t a = (uint32_t)(key / 20u), b = (uint32_t)(key % 1280000000ull); /* 7-mers: below 2^31 */
+    const uint32_t ha = mix32(a), hb = mix32(b);
+    const uint32_t m = ha <= hb ? a : b, hm = ha <= hb ? ha : hb;
+    /* 35 bits, the most mod_by takes: a second hash of the minimizer (hm
+     * itself leans low, being a minimum) over three low bits of the first */
+    const uint64_t x = (uint64_t)mix32(m ^ 0x85EBCA6Bu) << 3 | (hm & 7u);
+    return mod_by(x, n_lines, magic);
+}
+
+/* the home bucket of `key` in a probe table of num_sigs buckets; `home` as
+ * above, magic = mod_magic(num_sigs >> hs) */
+KGX_HD uint64_t home_bucket(uint64_t key, uint64_t num_sigs, uint64_t magic, uint32_t home)
+{
+    const uint32_t hs = home_shift_of(home);
+    return line_home(key, num_sigs >> hs, magic, home >> HOME_MODE_SHIFT) << hs;
+}
+
+}  // namespace kgx
+
+#endif

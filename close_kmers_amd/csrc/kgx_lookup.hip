@@ -747,7 +747,7 @@ __global__ __launch_bounds__(256) void probe_kernel(
             const uint64_t m = filter_bits(filter_hash(key[j]));
             pend[j] = (fw[j] & m) == m; /* else stored nowhere: a miss */
         }
-        slot[j] = pend[j] ? mod_by(key[j], num_sigs >> hs, magic) << hs : 0; /* hs: kgx_image_set_line_index */
+        slot[j] = pend[j] ? home_bucket(key[j], num_sigs, magic, hs) : 0; /* hs: kgx_line_home.h */
     }
 
     uint4 rec[J]; /* the matching bucket's payload */
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(256) void probe_kernel(
  * 64-B lines read this way run at 45 G/s, tools/line_probe.py).
  *
  * Window w of the tile (w = 64 j + l, owned by lane l in slice j) is looked
- * up by group q = w % (64 / G) in instruction i = w / (64 / G).  The group
+ * up by group q = l % (64 / G) in instruction i = l / (64 / G) of slice j.  The group
  * examines buckets in probe order: from the home slot to the end of its line,
  * then whole lines, wrapping at num_sigs; the first bucket whose key matches
  * (hit) or exceeds MAX_ENCODED (miss) ends the chain -- lookup_hash_entry,
@@ -843,7 +843,6 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
 {
     constexpr uint32_t T = 64 * J;
     constexpr uint32_t NQ = 64 / G; /* windows per instruction */
-    constexpr int NI = J * G;       /* instructions per tile */
     __shared__ uint8_t code_tab[256]; /* residue -> code; DNA: base -> class */
     __shared__ uint8_t cod_tab[DNA ? 68 : 1];
     __shared__ uint4 lds_rec[PROBE_WAVES][T];
@@ -881,35 +880,43 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
     uint64_t home[J];
 #pragma unroll
     for (int j = 0; j < J; j++) {
-        home[j] = ok[j] ? mod_by(key[j], num_sigs >> hs, magic) << hs : 0; /* hs 2: line-aligned homes */
+        home[j] = ok[j] ? home_bucket(key[j], num_sigs, magic, hs) : 0; /* line starts with the index */
         lds_hit[wave][64 * j + lane] = 0;
     }
 
     const uint32_t q = lane / G, c = lane % G;
-    uint64_t K[NI], cur[NI];
-    uint32_t live = 0; /* bit i: instruction i's chain is still open */
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-        const uint32_t owner = NQ * (i % G) + q; /* slice i / G */
-        K[i] = __shfl(key[i / G], (int)owner);
-        cur[i] = __shfl(home[i / G], (int)owner);
-        live |= (uint32_t)__shfl((int)ok[i / G], (int)owner) << i;
-    }
     /* lines a chain may visit before it has covered the whole table */
     const uint64_t max_lines = num_sigs / G + 2;
+    /* One 64-window slice (G instructions) at a time, each with its own
+     * rounds: the wave holds G lines in flight instead of J * G, so a tile of
+     * any J needs the registers of J = 1 (8 waves per SIMD at G = 4, where
+     * all of a 128-window tile's chains at once left 5).  With the minimizer
+     * home nearly every wave runs a second, almost empty round, and it is
+     * the other resident waves that cover it. */
+#pragma unroll
+    for (int j = 0; j < J; j++) {
+    uint64_t K[G], cur[G];
+    uint32_t live = 0; /* bit i: instruction i's chain is still open */
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        const uint32_t owner = NQ * i + q;
+        K[i] = __shfl(key[j], (int)owner);
+        cur[i] = __shfl(home[j], (int)owner);
+        live |= (uint32_t)__shfl((int)ok[j], (int)owner) << i;
+    }
     for (uint64_t round = 0;; round++) {
         /* only open chains load; d is fresh each round (no merge with an
          * older value at the branch join, so no wait for the load there) */
-        uint4 d[NI];
+        uint4 d[G];
 #pragma unroll
-        for (int i = 0; i < NI; i++) {
+        for (int i = 0; i < G; i++) {
             const uint64_t line = cur[i] - cur[i] % G;
             if ((live >> i & 1u) && line + c < num_sigs)
                 d[i] = packed[line + c];
         }
         bool more = false;
 #pragma unroll
-        for (int i = 0; i < NI; i++) {
+        for (int i = 0; i < G; i++) {
             const bool act = live >> i & 1u;
             const uint64_t line = cur[i] - cur[i] % G;
             const uint64_t b = line + c;
@@ -924,7 +931,7 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
                 if (ev) {
                     const uint32_t first = __builtin_ctz(ev);
                     if (c == first && (gm >> first & 1u)) {
-                        const uint32_t w = NQ * i + q;
+                        const uint32_t w = 64 * j + NQ * i + q;
                         lds_rec[wave][w] = d[i];
                         lds_hit[wave][w] = 1;
                     }
@@ -940,6 +947,7 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
         if (!__any(more))
             break;
     }
+    } /* slices */
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -963,7 +971,7 @@ static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *resi
 {
     hipLaunchKernelGGL((probe_line_kernel<J, G, DNA>), grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues,
                        n_residues, seq_off, wbase, tile_seq, n_seq, static_cast<const uint4 *>(table),
-                       num_sigs, mod_magic(num_sigs >> hs), hs, hot, cold, hit_mask, nt);
+                       num_sigs, mod_magic(num_sigs >> home_shift_of(hs)), hs, hot, cold, hit_mask, nt);
 }
 
 template <int J, int MODE>
@@ -973,7 +981,7 @@ static void launch_probe_m(dim3 grid, hipStream_t stream, const uint8_t *residue
                            const uint64_t *filter, uint32_t filter_log2, uint4 *hot, uint4 *cold,
                            uint64_t *hit_mask)
 {
-    const uint64_t magic = mod_magic(num_sigs >> hs);
+    const uint64_t magic = mod_magic(num_sigs >> home_shift_of(hs));
     if (filter)
         hipLaunchKernelGGL((probe_kernel<J, MODE, true>), grid, dim3(64 * PROBE_WAVES), 0, stream, residues,
                            n_residues, seq_off, wbase, tile_seq, n_seq, table, num_sigs, magic, hs, filter,
@@ -1153,13 +1161,13 @@ __global__ __launch_bounds__(256) void count_keys_kernel(const packed_bucket *__
  * lookup_hash_entry (kguts.cc:585-602) walks from key mod num_sigs and stops at
  * the key or at a stop bucket, so a duplicate further on or an entry behind a
  * stop is never found -- is inserted into the line table by linear probing
- * from the start of line (key mod n_lines), 4 buckets a line, by a 64-bit CAS
- * on the record's first word.  A probe of the line table from that home finds
- * exactly the records the reference finds, so results are unchanged while
- * almost every chain ends in its first 64-B line. */
+ * from the start of the key's home line (line_home, kgx_line_home.h), 4
+ * buckets a line, by a 64-bit CAS on the record's first word.  A probe of the
+ * line table from that home finds exactly the records the reference finds, so
+ * results are unchanged while nearly every chain ends in its first 64-B line. */
 __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *__restrict__ src, uint64_t num_sigs,
                                                           uint64_t src_magic, packed_bucket *lines, uint64_t n_lines,
-                                                          uint64_t line_magic, uint32_t *overflow)
+                                                          uint64_t line_magic, uint32_t home_mode, uint32_t *overflow)
 {
     const uint64_t NB = 4 * n_lines;
     for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < num_sigs;
@@ -1178,7 +1186,7 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
         }
         if (!first)
             continue;
-        uint64_t x = mod_by(key, n_lines, line_magic) * 4;
+        uint64_t x = line_home(key, n_lines, line_magic, home_mode) * 4;
         bool placed = false;
         for (uint64_t n = 0; n < NB && !placed; n++) {
             const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&lines[x].lo),
@@ -1209,11 +1217,11 @@ hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long l
 }
 
 hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t *overflow, hipStream_t stream)
+                              uint32_t home_mode, uint32_t *overflow, hipStream_t stream)
 {
     hipLaunchKernelGGL(fill_empty_kernel, dim3(8192), dim3(256), 0, stream, lines, 4 * n_lines);
     hipLaunchKernelGGL(lines_build_kernel, dim3(8192), dim3(256), 0, stream, src, num_sigs, mod_magic(num_sigs), lines,
-                       n_lines, mod_magic(n_lines), overflow);
+                       n_lines, mod_magic(n_lines), home_mode, overflow);
     return hipGetLastError();
 }
 

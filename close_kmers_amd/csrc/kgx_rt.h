@@ -353,10 +353,12 @@ struct kgx_image {
     kgx_sig_kmer *d_table = nullptr;   /* AOS24: the file's buckets */
     kgx::packed_bucket *d_packed = nullptr; /* PACKED16 */
     /* kgx_image_set_line_index: the PACKED16 records again, 4 buckets a line,
-     * each key's home at the start of line (key mod n_lines); the probes read
-     * it instead of d_packed, which stays for downloads, saves and filters */
+     * each key's home at the start of its home line (line_home under
+     * lines_home, kgx_line_home.h); the probes read it instead of d_packed,
+     * which stays for downloads, saves and filters */
     kgx::packed_bucket *d_lines = nullptr;
     uint64_t n_lines = 0;
+    uint32_t lines_home = kgx::LINE_HOME_MOD; /* the home mode it was built with */
     uint32_t lines_load = 0; /* keys per 64 lines it was built for */
     uint64_t *d_filter = nullptr;           /* presence filter (kgx_image_set_filter) */
     uint32_t filter_log2_words = 0;
@@ -390,7 +392,7 @@ struct kgx_image {
     /* what the probes read: the line index when there is one */
     const void *probe_table() const { return d_lines ? static_cast<const void *>(d_lines) : resident(); }
     uint64_t probe_buckets() const { return d_lines ? 4 * n_lines : num_sigs; }
-    uint32_t home_shift() const { return d_lines ? 2u : 0u; }
+    uint32_t home_shift() const { return d_lines ? kgx::home_word(2u, lines_home) : 0u; }
 };
 
 struct kgx_ctx {
@@ -529,7 +531,7 @@ inline const void *ctx_probe_table(const kgx_ctx *c)
     return ctx_lines(c) ? static_cast<const void *>(c->img->d_lines) : c->img->resident();
 }
 inline uint64_t ctx_probe_buckets(const kgx_ctx *c) { return ctx_lines(c) ? 4 * c->img->n_lines : c->img->num_sigs; }
-inline uint32_t ctx_home_shift(const kgx_ctx *c) { return ctx_lines(c) ? 2u : 0u; }
+inline uint32_t ctx_home_shift(const kgx_ctx *c) { return ctx_lines(c) ? c->img->home_shift() : 0u; }
 /* a host batch's result: the context's host arrays */
 inline void fill_result(kgx_ctx *c, uint32_t n_seq, bool need_hits, bool want_best, uint64_t nwin, kgx_result *out)
 {

@@ -879,6 +879,16 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
         return fail(KGX_EINVAL, "null image");
     if (keys_per_64_lines > 255)
         return fail(KGX_EINVAL, "line index load: 0 (none) or 1 .. 255 keys per 64 lines");
+    /* the home of a key in this index: KGX_LINE_HOME 1 = the minimizer home
+     * (the default), 0 = key mod n_lines (kgx_line_home.h); read at each
+     * call, a property of the index it builds */
+    uint32_t home_mode = kgx::LINE_HOME_MINIMIZER;
+    if (const char *v = getenv("KGX_LINE_HOME")) {
+        if (!strcmp(v, "0"))
+            home_mode = kgx::LINE_HOME_MOD;
+        else if (strcmp(v, "1") && *v)
+            return fail(KGX_EINVAL, std::string("KGX_LINE_HOME: 0 (mod) or 1 (minimizer), not \"") + v + "\"");
+    }
     /* the service's workgroups hold the probe table's address */
     const auto hold = svc_shutdown_hold(img);
     HIP_TRY(hipSetDevice(img->device));
@@ -914,7 +924,7 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     }
     uint32_t over = 0;
     if (e == hipSuccess)
-        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, d_over, nullptr);
+        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, d_over, nullptr);
     if (e == hipSuccess)
         e = hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_count);
@@ -926,11 +936,13 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     }
     img->d_lines = lines;
     img->n_lines = n_lines;
+    img->lines_home = home_mode;
     img->lines_load = keys_per_64_lines;
     return KGX_OK;
 }
 
 uint64_t kgx_image_line_count(const kgx_image *img) { return img ? img->n_lines : 0; }
+uint32_t kgx_image_line_home(const kgx_image *img) { return img && img->d_lines ? img->lines_home : 0; }
 
 /* buckets [first, first + count) in the file's format into host memory */
 static int image_read(const kgx_image *img, uint64_t first, uint64_t count, kgx_sig_kmer *dst)
