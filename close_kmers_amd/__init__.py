@@ -11,11 +11,11 @@ launcher bench.py runs before any GPU call) pulls in nothing of the ABI.
 """
 import importlib
 
-_SUBMODULES = ("abi", "image_files", "synth", "shard", "build")
+_SUBMODULES = ("abi", "image_files", "synth", "shard", "build", "signatures")
 _ABI_NAMES = ("CALL_DTYPE", "HIT_DTYPE", "OTU_DTYPE", "SIG_DTYPE", "WANT_CALLS", "WANT_HITS", "WANT_OTU",
-              "Context", "Image", "KgxError", "device_count", "find_best_call", "parse_params")
+              "Context", "Image", "KgxError", "Signatures", "device_count", "find_best_call", "parse_params")
 
-__all__ = ["abi", "synth", "image_files", "shard", *_ABI_NAMES]
+__all__ = ["abi", "synth", "image_files", "shard", "signatures", *_ABI_NAMES]
 
 
 def __getattr__(name):

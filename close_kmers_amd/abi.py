@@ -37,6 +37,12 @@ BEST_DTYPE = np.dtype([("kind", "<i4"), ("fi0", "<i4"), ("fi1", "<i4"), ("score"
 SIG_DTYPE = np.dtype([("which_kmer", "<u8"), ("otu_index", "<i4"), ("avg_from_end", "<u2"),
                       ("pad", "<u2"), ("function_index", "<i4"), ("function_wt", "<f4")])
 assert HIT_DTYPE.itemsize == 32 and CALL_DTYPE.itemsize == 20 and SIG_DTYPE.itemsize == 24
+# kgx_sig_record (36 bytes of fields in a 40-byte struct)
+SIG_RECORD_DTYPE = np.dtype({"names": ["raw_key", "code", "function_index", "n_tuples", "n_best",
+                                       "median_offset", "function_wt"],
+                             "formats": ["<u8", "<u8", "<i4", "<u4", "<u4", "<i4", "<f4"],
+                             "offsets": [0, 8, 16, 20, 24, 28, 32], "itemsize": 40})
+SIG_STAGES = ("upload", "emit", "order", "segment", "records")
 
 
 class KgxError(RuntimeError):
@@ -67,6 +73,14 @@ class DeviceResult(ctypes.Structure):
 
 
 HIT_PLANES, HIT_PACKED16 = 0, 1
+
+
+class SigStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n_windows", "n_tuples", "n_sets", "n_kept", "n_storable",
+                                               "n_seqs_with_signature", "num_sigs_rule")]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class RollupResult(ctypes.Structure):
@@ -283,6 +297,12 @@ SIGNATURES = {
     "kgx_svc_config": (_INT, [_P, _U32, _U32, _U32]),
     "kgx_svc_stop": (_INT, [_P]),
     "kgx_svc_stat": (_INT, [_P, _CS, ctypes.POINTER(_U64)]),
+    "kgx_sig_select": (_INT, [_INT, _P, _P, _P, _U32, _U32, _PP]),
+    "kgx_sig_stats_get": (_INT, [_P, ctypes.POINTER(SigStats)]),
+    "kgx_sig_records": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
+    "kgx_sig_image": (_INT, [_P, _U64, _PP, ctypes.POINTER(_U64)]),
+    "kgx_sig_stage_ms": (_INT, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "kgx_sig_destroy": (_INT, [_P]),
 }
 
 
@@ -496,6 +516,58 @@ class Image:
     def close(self) -> None:
         if self.handle:
             lib().kgx_image_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Signatures:
+    """Signature k-mers selected on the device from function-labelled proteins
+    (kgx_sig_select): seq_function[i] is the function index of sequence i, or
+    negative for a sequence that takes no part."""
+
+    def __init__(self, residues, offsets, seq_function, n_functions: int, device: int = 0):
+        residues = np.ascontiguousarray(np.frombuffer(bytes(residues), np.uint8)
+                                        if isinstance(residues, (bytes, bytearray)) else residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        fn = np.ascontiguousarray(seq_function, dtype=np.int32)
+        if len(offsets) != len(fn) + 1:
+            raise ValueError("offsets holds one entry more than seq_function")
+        h = ctypes.c_void_p()
+        check(lib().kgx_sig_select(device, residues.ctypes.data if residues.size else None, offsets.ctypes.data,
+                                   fn.ctypes.data if fn.size else None, len(fn), n_functions, ctypes.byref(h)),
+              "kgx_sig_select")
+        self.handle = h.value
+
+    def stats(self) -> dict:
+        s = SigStats()
+        check(lib().kgx_sig_stats_get(self.handle, ctypes.byref(s)), "kgx_sig_stats_get")
+        return s.as_dict()
+
+    def stage_ms(self) -> dict:
+        ms = (ctypes.c_float * len(SIG_STAGES))()
+        check(lib().kgx_sig_stage_ms(self.handle, ms), "kgx_sig_stage_ms")
+        return dict(zip(SIG_STAGES, (float(x) for x in ms)))
+
+    def records(self) -> np.ndarray:
+        """The kept sets (SIG_RECORD_DTYPE), in ascending raw_key order."""
+        p, n = ctypes.c_void_p(), _U64()
+        check(lib().kgx_sig_records(self.handle, ctypes.byref(p), ctypes.byref(n)), "kgx_sig_records")
+        return _view(p.value, n.value, SIG_RECORD_DTYPE)
+
+    def image(self, num_sigs: int = 0) -> tuple[Image, int]:
+        """(image of the storable records, keys stored); num_sigs 0 = the builder's size rule."""
+        h, stored = ctypes.c_void_p(), _U64()
+        check(lib().kgx_sig_image(self.handle, num_sigs, ctypes.byref(h), ctypes.byref(stored)), "kgx_sig_image")
+        return Image(h.value), stored.value
+
+    def close(self) -> None:
+        if self.handle:
+            lib().kgx_sig_destroy(self.handle)
             self.handle = None
 
     def __enter__(self):

@@ -30,7 +30,8 @@ WAVE_SORT_CHECK = os.path.join(ROOT, "tests", "native", "wave_sort_check")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["kgx_lookup.hip", "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.hip", "kgx_fq.hip", "kgx_runtime.cpp",
+LIB_SOURCES = ["kgx_lookup.hip", "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.hip", "kgx_fq.hip", "kgx_sig.hip",
+               "kgx_runtime.cpp",
                "kgx_host_batch.cpp", "kgx_pool.cpp", "kgx_svc.cpp", "kguts_hip.cpp", "kgx_handlers.cpp"]
 HEADERS = ["kgx_internal.h", "kgx_device.h", "kgx_line_home.h", "kguts_hip.h", "kgx_rt.h", "kgx_lstd.h", "kgx_handlers.h",
            "kgx_wave_sort.h", "kgx_options.h", "kgx_dispatch.h", "kgx_score_map.h"]

@@ -32,6 +32,12 @@ namespace kgx {
 /* sets the thread's kgx_last_error() text and returns code */
 int fail(int code, const std::string &msg);
 bool is_gfx950(int dev);
+/* an image from n entries that are already in HBM of `device` (keys above
+ * 20^8 skipped, the lowest index of a duplicated key wins): the device half
+ * of kgx_image_build */
+int image_from_device_entries(int device, uint64_t num_sigs, const uint64_t *d_keys, const int32_t *d_fi,
+                              const int32_t *d_otu, const uint16_t *d_avg, const float *d_wt, uint64_t n,
+                              kgx_image **out, uint64_t *n_stored);
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \

@@ -1741,3 +1741,35 @@ int kgx_memcpy_d2h(void *dst, const void *src, uint64_t n)
 }
 
 }  /* extern "C" */
+
+namespace kgx {
+
+/* kgx_image_build's device half for entries already in HBM (kgx_sig.hip):
+ * the same table allocation, insert and settling */
+int image_from_device_entries(int device, uint64_t num_sigs, const uint64_t *d_keys, const int32_t *d_fi,
+                              const int32_t *d_otu, const uint16_t *d_avg, const float *d_wt, uint64_t n,
+                              kgx_image **out, uint64_t *n_stored)
+{
+    kgx_image *img = nullptr;
+    int rc = image_alloc(device, num_sigs, &img);
+    if (rc)
+        return rc;
+    DevBuf d_count;
+    hipError_t e = d_count.reserve(8);
+    unsigned long long cnt = 0;
+    if (e == hipSuccess)
+        e = launch_entries_image(img->d_table, num_sigs, d_keys, d_fi, d_otu, d_avg, d_wt, n,
+                                 d_count.as<unsigned long long>(), nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy(&cnt, d_count.p, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        kgx_image_close(img);
+        return fail(e == hipErrorOutOfMemory ? KGX_ENOMEM : KGX_EDEVICE,
+                    std::string("image build: ") + hipGetErrorString(e));
+    }
+    if (n_stored)
+        *n_stored = cnt;
+    return image_settle(img, out);
+}
+
+}  // namespace kgx

@@ -310,6 +310,59 @@ const void *kgx_image_table(const kgx_image *img);
  * {20^8+1, 0, 0, 0, 0, 0.0}) */
 int kgx_image_download(const kgx_image *img, void *dst, uint64_t nbytes);
 
+/* ---- signature selection: build_signature_kmers.cc on the device --------- */
+/* From function-labelled proteins to the entries of an image (DESIGN.md
+ * §8.8 states the rules): every window of 8 letters out of the 40 of
+ * ACDEFGHIKLMNPQRSTVWY / acdefghiklmnpqrstvwy in a sequence whose
+ * seq_function is >= 0 gives a tuple; a set = the tuples of one raw 8-byte
+ * key (upper and lower case differ); a set is kept when its most frequent
+ * function holds at least 80% of it (process_set's float test).  A kept
+ * set's record carries that function, the median of its tuples' distances
+ * from the end of their sequences, and compute_weight_of_signature's weight.
+ * Kept sets with a lower-case letter count everywhere but cannot be stored
+ * (the encoder rejects them): their code is above 20^8. */
+typedef struct kgx_sig kgx_sig;
+typedef struct kgx_sig_record {
+    uint64_t raw_key; /* the 8 bytes, first residue in the top byte */
+    uint64_t code;    /* base-20 code; > 20^8 when not storable */
+    int32_t function_index;
+    uint32_t n_tuples; /* NSi: the set's size */
+    uint32_t n_best;   /* NSiFj: its tuples of function_index */
+    int32_t median_offset;
+    float function_wt;
+} kgx_sig_record;
+typedef struct kgx_sig_stats {
+    uint64_t n_windows; /* window positions of the labelled sequences, sum of max(0, len - 7) */
+    uint64_t n_tuples;  /* those made of the 40 letters */
+    uint64_t n_sets;
+    uint64_t n_kept;     /* KS */
+    uint64_t n_storable; /* kept and upper case */
+    uint64_t n_seqs_with_signature; /* NSF */
+    uint64_t num_sigs_rule; /* the builder's table size: its first listed prime above 3 * n_kept (0: none) */
+} kgx_sig_stats;
+/* residues / seq_offsets as in kgx_process_batch; seq_function[i] is the
+ * function of sequence i, or negative for none (the sequence contributes
+ * nothing); a value >= n_functions is KGX_ERANGE, as are a sequence longer
+ * than 2^31-1 and a corpus of more than 2^31-1 windows.  The whole corpus is
+ * held in HBM in one pass (about 50 bytes per window): KGX_ENOMEM when it
+ * does not fit.  KGX_EDEVICE without a gfx950 device: there is no CPU path. */
+int kgx_sig_select(int device, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
+                   uint32_t n_seq, uint32_t n_functions, kgx_sig **out);
+int kgx_sig_stats_get(const kgx_sig *s, kgx_sig_stats *out);
+/* host view of the kept records in ascending raw_key order, valid until
+ * kgx_sig_destroy */
+int kgx_sig_records(kgx_sig *s, const kgx_sig_record **recs, uint64_t *n);
+/* The image of the storable records (otu_index -1, avg_from_end =
+ * (uint16_t)median_offset), inserted on the device as kgx_image_build
+ * inserts; num_sigs 0 = the builder's rule.  KGX_EFULL as kgx_image_build. */
+int kgx_sig_image(kgx_sig *s, uint64_t num_sigs, kgx_image **out, uint64_t *n_stored);
+/* device time of the last selection's stages, in ms: upload, emit, order
+ * (the two sorts), segment (set heads, vote, keep test, bitmap), records
+ * (popcount, compaction, weights) */
+#define KGX_SIG_STAGES 5
+int kgx_sig_stage_ms(const kgx_sig *s, float *ms);
+int kgx_sig_destroy(kgx_sig *s);
+
 /* ---- contexts: one per host thread, like one KmerGuts per pool thread --- */
 int kgx_ctx_create(kgx_image *img, kgx_ctx **out);
 int kgx_ctx_destroy(kgx_ctx *ctx);
