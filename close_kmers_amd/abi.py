@@ -208,6 +208,7 @@ SIGNATURES = {
     "kgx_image_set_line_index": (_INT, [_P, _U32]),
     "kgx_image_line_count": (_U64, [_P]),
     "kgx_image_line_home": (_U32, [_P]),
+    "kgx_image_line_stats": (_INT, [_P, ctypes.POINTER(_U64)]),
     "kgx_image_set_filter": (_INT, [_P, _INT]),
     "kgx_image_download": (_INT, [_P, _P, _U64]),
     "kgx_ctx_create": (_INT, [_P, _PP]),
@@ -475,6 +476,16 @@ class Image:
     def line_home(self) -> int:
         """the KGX_LINE_HOME mode the line index was built with (0 mod, 1 minimizer)"""
         return lib().kgx_image_line_home(self.handle)
+
+    LINE_STATS = ("stored", "past_home", "full_lines", "marked_lines", "mark_bits", "missing", "unjustified",
+                  "reserved")
+
+    def line_stats(self) -> dict:
+        """kgx_image_line_stats: a device pass over the line index; the
+        overflow marks are exact when missing and unjustified are both 0"""
+        out = (_U64 * 8)()
+        check(lib().kgx_image_line_stats(self.handle, out), "kgx_image_line_stats")
+        return dict(zip(self.LINE_STATS, (int(v) for v in out)))
 
     def download(self) -> np.ndarray:
         t = np.empty(self.num_sigs, dtype=SIG_DTYPE)

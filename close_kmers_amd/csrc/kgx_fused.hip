@@ -361,7 +361,9 @@ __device__ __forceinline__ void fused_small_body(const FusedArgs &a, const IN &k
                 }
                 if (hit[q]) {
                     const uint32_t at = nh + before + lanes_below(m[q]);
-                    hrec[at] = rec[q];
+                    /* (from either loop above) less the record's share of an
+                     * index line's overflow marks: the scorer's flag bits */
+                    hrec[at] = make_uint4(rec[q].x, rec[q].y, rec[q].z, rec[q].w & ~MARK_BITS_W);
                     hpos[at] = t + 256 * (jb + q);
                 }
                 nh += total;

@@ -158,7 +158,7 @@ hipError_t launch_plan_fused(const uint64_t *seq_off, uint32_t n_seq, uint64_t n
                              uint32_t *tile_seq, uint32_t tile_windows, uint64_t max_tiles, void *look,
                              uint32_t *status, hipStream_t stream);
 /* Probes of PACKED16 records take home_shift, the word of kgx_line_home.h
- * (home_word: shift | home mode << 8): a key's home bucket is
+ * (home_word: shift | home mode << 8 | overflow marks << 16): a key's home bucket is
  * line_home(key, num_sigs >> shift, mode) << shift and num_sigs counts the
  * table's buckets.  0: the reference's slot (key mod num_sigs); shift 2: the
  * line index of kgx_image_set_line_index (4-bucket lines, homes at line
@@ -188,9 +188,15 @@ hipError_t launch_filter_build(const void *table, int layout, uint64_t num_sigs,
 hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long long *count, hipStream_t stream);
 /* the line index of a PACKED16 table (lines_build_kernel): 4 * n_lines
  * buckets, homes by line_home(home_mode); *overflow |= 1 when some record
- * found no bucket */
+ * found no bucket; marks: then the overflow marks of kgx_line_home.h, by
+ * lines_mark_kernel */
 hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t home_mode, uint32_t *overflow, hipStream_t stream);
+                              uint32_t home_mode, bool marks, uint32_t *overflow, hipStream_t stream);
+/* kgx_image_line_stats: stats[0..7) += stored records, records past their
+ * home line, full lines, lines with a mark, mark bits set, missing and
+ * unjustified marks; scratch: (n_lines + 1) / 2 zeroed words */
+hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, uint32_t *scratch,
+                              unsigned long long *stats, hipStream_t stream);
 /* AoS -> packed; *not_packable |= 1 when some stored bucket does not fit */
 hipError_t launch_pack(const kgx_sig_kmer *table, packed_bucket *packed, uint64_t n,
                        uint32_t *not_packable, hipStream_t stream);

@@ -34,11 +34,17 @@ constexpr uint32_t LINE_HOME_MOD = 0, LINE_HOME_MINIMIZER = 1;
 
 /* What the probe launchers take as `home_shift`: bits 0-7 the shift hs (a
  * key's home bucket is home(key) << hs over num_sigs >> hs homes: 0 the
- * reference slots, 2 the 4-bucket lines of the index), bits 8 and up the
- * LINE_HOME_* mode of the image's index (0 where hs is 0). */
-constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8;
-KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode) { return shift | mode << HOME_MODE_SHIFT; }
+ * reference slots, 2 the 4-bucket lines of the index), bits 8-15 the
+ * LINE_HOME_* mode of the image's index (0 where hs is 0), bit 16 set when
+ * the index carries overflow marks (line_mark, below). */
+constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8, HOME_MODE_MASK = 0xFFu, HOME_MARKS_BIT = 1u << 16;
+KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode, bool marks = false)
+{
+    return shift | mode << HOME_MODE_SHIFT | (marks ? HOME_MARKS_BIT : 0u);
+}
 KGX_HD uint32_t home_shift_of(uint32_t home) { return home & HOME_SHIFT_MASK; }
+KGX_HD uint32_t home_mode_of(uint32_t home) { return home >> HOME_MODE_SHIFT & HOME_MODE_MASK; }
+KGX_HD bool home_marks_of(uint32_t home) { return (home & HOME_MARKS_BIT) != 0; }
 
 /* x % n for x < 2^35, n >= 1, m = floor((2^64-1)/n): the quotient estimate
  * is exact or one short, so one conditional subtraction finishes it */
@@ -85,8 +91,31 @@ KGX_HD uint64_t line_home(uint64_t key, uint64_t n_lines, uint64_t magic, uint32
 KGX_HD uint64_t home_bucket(uint64_t key, uint64_t num_sigs, uint64_t magic, uint32_t home)
 {
     const uint32_t hs = home_shift_of(home);
-    return line_home(key, num_sigs >> hs, magic, home >> HOME_MODE_SHIFT) << hs;
+    return line_home(key, num_sigs >> hs, magic, home_mode_of(home)) << hs;
 }
+
+/* Overflow marks.  A PACKED16 record leaves bits 60-63 of its second word
+ * unused, so the four records of an index line carry 16 spare bits.  Bit
+ * line_mark(K) of line L is set if and only if some stored key with that mark
+ * visited L during its insertion and was placed in a later line (only full
+ * lines are passed, so only full lines carry marks).  A probe that has
+ * searched a full line for K without finding it, and finds K's mark clear
+ * there, knows K is not stored: a stored K not in L whose chain visits L left
+ * L and set the bit.
+ *
+ * The mark is a hash of the whole key, independent of the home hash: the up
+ * to 40 keys that share a minimizer differ in one end residue only, and they
+ * spread over the 16 values.  Mark g lives in record g >> 2 of the line, bit
+ * 60 + (g & 3) of its second word (bit 28 + (g & 3) of its last dword). */
+constexpr uint32_t LINE_MARKS = 16;
+constexpr uint64_t MARK_BITS_HI = 0xFull << 60; /* a record's share of its line's marks */
+constexpr uint32_t MARK_BITS_W = 0xFu << 28;    /* the same in the record's last dword */
+KGX_HD uint32_t line_mark(uint64_t key)
+{
+    return mix32(((uint32_t)key ^ 0x27D4EB2Fu) + (uint32_t)(key >> 32) * 0xC2B2AE35u) >> 28;
+}
+KGX_HD uint32_t mark_record(uint32_t g) { return g >> 2; }
+KGX_HD uint32_t mark_bit_w(uint32_t g) { return 28u + (g & 3u); }
 
 }  // namespace kgx
 

@@ -682,12 +682,16 @@ __device__ __forceinline__ void store_tile_hits(const bool *hit, const uint64_t 
         const uint64_t m = __ballot(hit[j]);
         if (hit[j]) {
             const uint64_t at = g0 + count + lanes_below(m);
+            /* HIT_PACKED16: the table record itself, less its share of an
+             * index line's overflow marks (kgx_line_home.h): those bits are
+             * the scorer's flags in a hit and leave the probe clear */
+            const uint32_t w = pv[j].w & ~MARK_BITS_W;
             if (PACKED && nt) {
                 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-                const u32x4_t v = {pv[j].x, pv[j].y, pv[j].z, pv[j].w};
+                const u32x4_t v = {pv[j].x, pv[j].y, pv[j].z, w};
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t *>(hot + at));
             } else if (PACKED) {
-                hot[at] = pv[j]; /* HIT_PACKED16: the table record itself */
+                hot[at] = make_uint4(pv[j].x, pv[j].y, pv[j].z, w);
             } else {
                 hot[at] = make_uint4(pv[j].y & 0xFFFFu, pv[j].z, pv[j].w, pos[j]);
                 cold[at] = make_uint4((uint32_t)kv[j], (uint32_t)(kv[j] >> 32), pv[j].x, sq[j]);
@@ -834,7 +838,7 @@ __global__ __launch_bounds__(256) void probe_kernel(
  * num_sigs buckets -- same answer, since every bucket has been seen).
  * The matching lane writes the record to LDS for the window's owner.
  */
-template <int J, int G, bool DNA>
+template <int J, int G, bool DNA, bool MARKS>
 __global__ __launch_bounds__(256) void probe_line_kernel(
     const uint8_t *__restrict__ residues, uint64_t n_residues, const uint64_t *__restrict__ seq_off,
     const uint64_t *__restrict__ wbase, const uint32_t *__restrict__ tile_seq, uint32_t n_seq,
@@ -885,6 +889,11 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
     }
 
     const uint32_t q = lane / G, c = lane % G;
+    /* MARKS: the table is a line index with overflow marks (the launcher
+     * picks it only for G = 4 with whole 4-record lines and line-aligned
+     * homes, so a line searched in vain was searched whole); without, the
+     * kernel holds none of the mark test's instructions or registers */
+    static_assert(!MARKS || G == 4, "the index's lines are 4 records");
     /* lines a chain may visit before it has covered the whole table */
     const uint64_t max_lines = num_sigs / G + 2;
     /* One 64-window slice (G instructions) at a time, each with its own
@@ -896,13 +905,20 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
 #pragma unroll
     for (int j = 0; j < J; j++) {
     uint64_t K[G], cur[G];
-    uint32_t live = 0; /* bit i: instruction i's chain is still open */
+    /* bit i: instruction i's chain is still open.  With overflow marks the
+     * owner also hands on line_mark of its key */
+    uint32_t live = 0;
+    const uint32_t own = MARKS ? (uint32_t)ok[j] | line_mark(key[j]) << 8 : (uint32_t)ok[j];
+    uint32_t mbit[MARKS ? G : 1]; /* this lane's bit of its record's last dword, if it holds the key's mark */
 #pragma unroll
     for (int i = 0; i < G; i++) {
         const uint32_t owner = NQ * i + q;
         K[i] = __shfl(key[j], (int)owner);
         cur[i] = __shfl(home[j], (int)owner);
-        live |= (uint32_t)__shfl((int)ok[j], (int)owner) << i;
+        const uint32_t o = (uint32_t)__shfl((int)own, (int)owner);
+        live |= (o & 1u) << i;
+        if constexpr (MARKS)
+            mbit[i] = c == mark_record(o >> 8) ? 1u << mark_bit_w(o >> 8) : 0u;
     }
     for (uint64_t round = 0;; round++) {
         /* only open chains load; d is fresh each round (no merge with an
@@ -926,6 +942,14 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
             const uint64_t me = __ballot(valid && kb > MAX_ENCODED);
             const uint32_t gm = (uint32_t)(mm >> (G * q)) & ((1u << G) - 1);
             const uint32_t ge = (uint32_t)(me >> (G * q)) & ((1u << G) - 1);
+            /* the line's overflow mark for K[i]: the lane holding record
+             * mark >> 2 tests its bit.  A full line searched in vain whose
+             * mark for the key is clear was never passed by it: a miss. */
+            bool passed = true;
+            if constexpr (MARKS) {
+                const uint64_t mk = __ballot(valid && (d[i].w & mbit[i]));
+                passed = ((uint32_t)(mk >> (G * q)) & ((1u << G) - 1)) != 0;
+            }
             if (act) {
                 const uint32_t ev = gm | ge;
                 if (ev) {
@@ -936,7 +960,7 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
                         lds_hit[wave][w] = 1;
                     }
                     live &= ~(1u << i);
-                } else if (round + 1 >= max_lines) {
+                } else if (round + 1 >= max_lines || !passed) {
                     live &= ~(1u << i);
                 } else {
                     cur[i] = line + G >= num_sigs ? 0 : line + G;
@@ -969,9 +993,17 @@ static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *resi
                               uint32_t n_seq, const void *table, uint64_t num_sigs, uint32_t hs, uint4 *hot,
                               uint4 *cold, uint64_t *hit_mask, uint32_t dyn_lds, uint32_t nt = 0)
 {
-    hipLaunchKernelGGL((probe_line_kernel<J, G, DNA>), grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues,
-                       n_residues, seq_off, wbase, tile_seq, n_seq, static_cast<const uint4 *>(table),
-                       num_sigs, mod_magic(num_sigs >> home_shift_of(hs)), hs, hot, cold, hit_mask, nt);
+    /* the kernel with the mark test only over an index that has marks: whole
+     * 4-record lines and line-aligned homes; every other table runs the
+     * kernel without it */
+    const bool marks = G == 4 && home_marks_of(hs) && home_shift_of(hs) == 2 && num_sigs % 4 == 0;
+    auto *kernel = probe_line_kernel<J, G, DNA, false>;
+    if constexpr (G == 4)
+        if (marks)
+            kernel = probe_line_kernel<J, G, DNA, true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues, n_residues, seq_off, wbase,
+                       tile_seq, n_seq, static_cast<const uint4 *>(table), num_sigs,
+                       mod_magic(num_sigs >> home_shift_of(hs)), hs, hot, cold, hit_mask, nt);
 }
 
 template <int J, int MODE>
@@ -1202,6 +1234,83 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
     }
 }
 
+/* The overflow marks of a finished line index (kgx_line_home.h): every record
+ * that lies past its key's home line sets its key's mark on each line from
+ * the home to the one before its own, the lines its insertion passed.  A
+ * kernel of its own, after the inserts: the inserter's plain store of `hi`
+ * would race with another key's OR.  SCRATCH: the same marks into a separate
+ * array instead, 16 bits per line, two lines per word (kgx_image_line_stats
+ * compares the two). */
+template <bool SCRATCH>
+__global__ __launch_bounds__(256) void lines_mark_kernel(packed_bucket *lines, uint64_t n_lines, uint64_t line_magic,
+                                                         uint32_t home_mode, uint32_t *scratch,
+                                                         unsigned long long *stats)
+{
+    const uint64_t NB = 4 * n_lines;
+    uint64_t stored = 0, past = 0;
+    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < NB; b += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = lines[b].lo & PACK_KEY_MASK;
+        if (key > MAX_ENCODED)
+            continue;
+        stored++;
+        const uint64_t own = b / 4;
+        uint64_t l = line_home(key, n_lines, line_magic, home_mode);
+        if (l == own)
+            continue;
+        past++;
+        const uint32_t g = line_mark(key);
+        for (; l != own; l = l + 1 == n_lines ? 0 : l + 1) {
+            if (SCRATCH)
+                atomicOr(scratch + (l >> 1), 1u << (g + 16u * (uint32_t)(l & 1)));
+            else
+                atomicOr(reinterpret_cast<unsigned long long *>(&lines[4 * l + mark_record(g)].hi),
+                         1ull << (32 + mark_bit_w(g)));
+        }
+    }
+    if (SCRATCH) {
+        for (int o = 32; o > 0; o >>= 1) {
+            stored += __shfl_xor(stored, o);
+            past += __shfl_xor(past, o);
+        }
+        if (lane_id() == 0 && stored) {
+            atomicAdd(stats + 0, (unsigned long long)stored);
+            atomicAdd(stats + 1, (unsigned long long)past);
+        }
+    }
+}
+
+/* kgx_image_line_stats, after lines_mark_kernel<true>: per line, whether it
+ * is full, its marks, and their difference from the marks the stored records
+ * call for (scratch): missing = called for and clear, unjustified = set and
+ * not called for */
+__global__ __launch_bounds__(256) void lines_stats_kernel(const packed_bucket *__restrict__ lines, uint64_t n_lines,
+                                                          const uint32_t *__restrict__ scratch,
+                                                          unsigned long long *stats)
+{
+    uint64_t v[5] = {0, 0, 0, 0, 0}; /* full lines, marked lines, bits, missing, unjustified */
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < n_lines;
+         l += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t have = 0, full = 1;
+        for (uint32_t r = 0; r < 4; r++) {
+            const packed_bucket e = lines[4 * l + r];
+            full &= (e.lo & PACK_KEY_MASK) <= MAX_ENCODED;
+            have |= (uint32_t)(e.hi >> 60) << (4 * r);
+        }
+        const uint32_t want = scratch[l >> 1] >> (16u * (uint32_t)(l & 1)) & 0xFFFFu;
+        v[0] += full;
+        v[1] += have != 0;
+        v[2] += (uint32_t)__popc(have);
+        v[3] += (uint32_t)__popc(want & ~have);
+        v[4] += (uint32_t)__popc(have & ~want);
+    }
+    for (int k = 0; k < 5; k++) {
+        for (int o = 32; o > 0; o >>= 1)
+            v[k] += __shfl_xor(v[k], o);
+        if (lane_id() == 0 && v[k])
+            atomicAdd(stats + 2 + k, (unsigned long long)v[k]);
+    }
+}
+
 __global__ __launch_bounds__(256) void fill_empty_kernel(packed_bucket *t, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -1217,11 +1326,23 @@ hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long l
 }
 
 hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t home_mode, uint32_t *overflow, hipStream_t stream)
+                              uint32_t home_mode, bool marks, uint32_t *overflow, hipStream_t stream)
 {
     hipLaunchKernelGGL(fill_empty_kernel, dim3(8192), dim3(256), 0, stream, lines, 4 * n_lines);
     hipLaunchKernelGGL(lines_build_kernel, dim3(8192), dim3(256), 0, stream, src, num_sigs, mod_magic(num_sigs), lines,
                        n_lines, mod_magic(n_lines), home_mode, overflow);
+    if (marks)
+        hipLaunchKernelGGL(lines_mark_kernel<false>, dim3(8192), dim3(256), 0, stream, lines, n_lines,
+                           mod_magic(n_lines), home_mode, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, uint32_t *scratch,
+                              unsigned long long *stats, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lines_mark_kernel<true>, dim3(8192), dim3(256), 0, stream, const_cast<packed_bucket *>(lines),
+                       n_lines, mod_magic(n_lines), home_mode, scratch, stats);
+    hipLaunchKernelGGL(lines_stats_kernel, dim3(8192), dim3(256), 0, stream, lines, n_lines, scratch, stats);
     return hipGetLastError();
 }
 

@@ -889,6 +889,16 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
         else if (strcmp(v, "1") && *v)
             return fail(KGX_EINVAL, std::string("KGX_LINE_HOME: 0 (mod) or 1 (minimizer), not \"") + v + "\"");
     }
+    /* overflow marks on the index's full lines, which end an absent key's
+     * chain in one line (kgx_line_home.h): KGX_LINE_MARKS 1 (the default)
+     * builds them, 0 builds none; read at each call like KGX_LINE_HOME */
+    bool marks = true;
+    if (const char *v = getenv("KGX_LINE_MARKS")) {
+        if (!strcmp(v, "0"))
+            marks = false;
+        else if (strcmp(v, "1") && *v)
+            return fail(KGX_EINVAL, std::string("KGX_LINE_MARKS: 0 (none) or 1 (marks), not \"") + v + "\"");
+    }
     /* the service's workgroups hold the probe table's address */
     const auto hold = svc_shutdown_hold(img);
     HIP_TRY(hipSetDevice(img->device));
@@ -924,7 +934,7 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     }
     uint32_t over = 0;
     if (e == hipSuccess)
-        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, d_over, nullptr);
+        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, marks, d_over, nullptr);
     if (e == hipSuccess)
         e = hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_count);
@@ -937,12 +947,42 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     img->d_lines = lines;
     img->n_lines = n_lines;
     img->lines_home = home_mode;
+    img->lines_marks = marks;
     img->lines_load = keys_per_64_lines;
     return KGX_OK;
 }
 
 uint64_t kgx_image_line_count(const kgx_image *img) { return img ? img->n_lines : 0; }
 uint32_t kgx_image_line_home(const kgx_image *img) { return img && img->d_lines ? img->lines_home : 0; }
+
+int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
+{
+    if (!img || !out)
+        return fail(KGX_EINVAL, "null image or output");
+    if (!img->d_lines)
+        return fail(KGX_EINVAL, "the image has no line index");
+    HIP_TRY(hipSetDevice(img->device));
+    /* the marks the stored records call for, 16 bits a line, and 8 counters */
+    const uint64_t words = (img->n_lines + 1) / 2;
+    uint32_t *d_scratch = nullptr;
+    if (hipMalloc(&d_scratch, words * 4 + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KGX_ENOMEM, "no room for the line statistics (" + std::to_string(words * 4) + " B)");
+    }
+    unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_scratch);
+    hipError_t e = hipMemset(d_scratch, 0, words * 4 + 64);
+    if (e == hipSuccess)
+        e = launch_lines_stats(img->d_lines, img->n_lines, img->lines_home, d_scratch + 16, d_stats, nullptr);
+    unsigned long long h[8] = {};
+    if (e == hipSuccess)
+        e = hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost);
+    (void)hipFree(d_scratch);
+    if (e != hipSuccess)
+        return fail(KGX_EDEVICE, std::string("line statistics: ") + hipGetErrorString(e));
+    for (int i = 0; i < 8; i++)
+        out[i] = h[i];
+    return KGX_OK;
+}
 
 /* buckets [first, first + count) in the file's format into host memory */
 static int image_read(const kgx_image *img, uint64_t first, uint64_t count, kgx_sig_kmer *dst)

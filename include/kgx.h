@@ -288,13 +288,38 @@ int kgx_image_set_layout(kgx_image *img, int layout);
  * Loads past ~48 (75% of the buckets) are accepted for tests of full lines,
  * but linear probing there walks ~1/(1-a)^2 buckets per miss: the build's
  * insert walks and the probes' chains grow steeply (results stay exact);
- * 36 is the measured load. */
+ * 36 is the measured load.
+ * The index also carries overflow marks: 16 spare bits per line (bits 60-63
+ * of each record's second word, which PACKED16 leaves 0) say which of 16
+ * hash classes of keys were pushed on past that full line when the index was
+ * built.  The line probe ends an absent key's chain at the first full line
+ * whose mark for it is clear instead of walking on to an empty bucket; hit
+ * records leave every probe with those bits cleared.  The environment
+ * variable KGX_LINE_MARKS, read at each call like KGX_LINE_HOME, turns them
+ * off: 1 builds marks (the default), 0 builds none; any other value is
+ * KGX_EINVAL and the index the image had is kept.  Which bits are set depends
+ * on the build's insertion order and differs from build to build; results do
+ * not. */
 int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines);
 /* lines of the image's line index (0: none) */
 uint64_t kgx_image_line_count(const kgx_image *img);
 /* the KGX_LINE_HOME mode the image's line index was built with (0: mod or
  * no index, 1: minimizer) */
 uint32_t kgx_image_line_home(const kgx_image *img);
+/* A device pass over the line index: out[0] stored records, [1] records past
+ * their home line, [2] full lines, [3] lines with any overflow mark, [4] mark
+ * bits set, [5] missing marks (a stored key lies past a line whose bit for it
+ * is clear; 0 for an index with marks, else probes would miss stored keys),
+ * [6] unjustified marks (a set bit that no stored key past that line calls
+ * for; 0, or the marks would end fewer chains than they can), [7] reserved,
+ * 0.  An index built with KGX_LINE_MARKS=0 has [3] = [4] = [6] = 0 and [5]
+ * the marks it would carry.  The marks called for are recomputed by the walk
+ * that set them (from each displaced record's home line to the line before
+ * its own), so [5] = [6] = 0 says that the index holds exactly that walk's
+ * marks and no stray bit; that the walk itself is the right one is what the
+ * comparisons with the reference's results check.  KGX_EINVAL without a line
+ * index; needs 2 B per line of device memory while it runs. */
+int kgx_image_line_stats(const kgx_image *img, uint64_t out[8]);
 /* Presence filter: 2^log2_bits bits (0 removes it), two bits per stored key
  * in one 64-bit word (blocked Bloom filter).  A probe whose key misses the
  * filter skips the table -- exactly the miss it would have found -- so

@@ -16,6 +16,16 @@ benchmark's (half the sequences planted copies of source proteins with 10%
 substitutions, half uniform), where two neighbouring windows homed on one line
 ask for it once when one wave instruction serves both (15 pairs in 16).
 
+Under each home it then adds overflow marks (csrc/kgx_line_home.h line_mark):
+a full line remembers, in 1 or in 16 bits, which keys were pushed on past it,
+and an absent key's chain ends at the first full line whose bit for it is
+clear instead of at the first line with an empty bucket.  Printed for no
+marks, 1 bit and 16 bits: lines per window, windows past their first line,
+lines per absent key, and requests per window under two models of merging
+(within one wave instruction, as above; within a 128-window tile, where every
+line a tile's windows touch is asked for once), and the fraction of lines that
+are full and were ever passed, the only ones a mark can sit on.
+
 The benchmark's image has 20^7 = 1.28e9 7-mers, 1.0e9 keys (a quarter of them
 consecutive windows of source proteins, as synth.py plants them) and 1.78e9
 lines: 0.78 keys and 1.39 lines per 7-mer.  The model keeps those two ratios
@@ -54,6 +64,13 @@ def homes(keys, n_lines, mode, alpha):
     hm = np.minimum(ha, hb)
     x = (mix32(m ^ np.uint64(0x85EBCA6B)) << np.uint64(3)) | (hm & np.uint64(7))
     return (x % np.uint64(n_lines)).astype(np.int64)
+
+
+def line_mark(keys):
+    """kgx_line_home.h line_mark over uint64 arrays"""
+    keys = keys.astype(np.uint64)
+    x = (((keys & M32) ^ np.uint64(0x27D4EB2F)) + (keys >> np.uint64(32)) * np.uint64(0xC2B2AE35)) & M32
+    return (mix32(x) >> np.uint64(28)).astype(np.int64)
 
 
 def windows(codes, alpha):
@@ -95,6 +112,48 @@ def full_run(occ, n_lines):
     # the next line at or after i that is not full, by a reverse running minimum
     nxt = np.minimum.accumulate(np.where(~f2, idx, 2 * n_lines)[::-1])[::-1]
     return np.minimum(nxt - idx, n_lines)[:n_lines]
+
+
+def set_marks(keys, home, at, n_lines, bits):
+    """the marks of a built index: every key placed past its home line sets
+    bit line_mark(key) (bit 0 when bits == 1) on each line from its home to
+    the one before its own"""
+    marks = np.zeros(n_lines, np.uint32)
+    g = line_mark(keys) if bits == 16 else np.zeros(len(keys), np.int64)
+    walk = (at // 4 - home) % n_lines
+    todo = np.nonzero(walk > 0)[0]
+    d = 0
+    while len(todo):
+        np.bitwise_or.at(marks, (home[todo] + d) % n_lines, (np.uint32(1) << g[todo].astype(np.uint32)))
+        d += 1
+        todo = todo[walk[todo] > d]
+    return marks
+
+
+def marked_chain(keys, home, full, marks, n_lines, bits):
+    """lines an absent key's chain touches: on from a full line only while the
+    line's mark for the key is set"""
+    g = line_mark(keys) if bits == 16 else np.zeros(len(keys), np.int64)
+    lines = np.ones(len(keys), np.int64)
+    todo = np.arange(len(keys))
+    line = home.copy()
+    while len(todo):
+        go = full[line[todo]] & ((marks[line[todo]] >> g[todo].astype(np.uint32)) & np.uint32(1)).astype(bool)
+        todo = todo[go]
+        line[todo] = (line[todo] + 1) % n_lines
+        lines[todo] += 1
+    return lines
+
+
+def tile_requests(qh, q_lines, n_lines, tile=128):
+    """requests per window when every line the windows of one 128-window tile
+    touch is asked for once (the batch's windows in sequence order)"""
+    h, n = qh.ravel(), q_lines.ravel()
+    t = np.arange(len(h)) // tile
+    rep = np.repeat(np.arange(len(h)), n)
+    step = np.arange(len(rep)) - np.repeat(np.cumsum(n) - n, n)
+    touched = t[rep] * np.int64(n_lines) + (h[rep] + step) % n_lines
+    return len(np.unique(touched)) / len(h)
 
 
 def model(alpha, seed):
@@ -143,7 +202,34 @@ def model(alpha, seed):
             pair[:, j] &= ~pair[:, j - 1]
         saved = np.where(pair, np.minimum(q_lines[:, 1:], q_lines[:, :-1]), 0)
         requests = (q_lines.sum() - 15.0 / 16.0 * saved.sum()) / q_lines.size
+        # overflow marks: none, 1 bit and 16 bits per line
+        full = run > 0
+        order_pos = order[np.minimum(pos, len(skeys) - 1)]
+        variants = {}
+        for bits in (0, 1, 16):
+            if bits:
+                mk = set_marks(keys, h, at, n_lines, bits)
+                la = marked_chain(absent, homes(absent, n_lines, mode, alpha), full, mk, n_lines, bits)
+                ql = np.where(present, lines_present[order_pos].reshape(qk.shape),
+                              marked_chain(qk.ravel(), qh.ravel(), full, mk, n_lines, bits).reshape(qk.shape))
+            else:
+                mk, la, ql = np.zeros(n_lines, np.uint32), lines_absent, q_lines
+            sv = np.where(pair, np.minimum(ql[:, 1:], ql[:, :-1]), 0)
+            variants[str(bits)] = {
+                "query_lines_per_window": float(ql.mean()),
+                "query_windows_past_first_line": float((ql > 1).mean()),
+                "lines_per_absent_key": float(la.mean()),
+                "query_lines_per_absent_window": float(ql[~present].mean()),
+                "query_lines_per_present_window": float(ql[present].mean()),
+                "query_requests_per_window": float((ql.sum() - 15.0 / 16.0 * sv.sum()) / ql.size),
+                "query_requests_per_window_tile_merge": float(tile_requests(qh, ql, n_lines)),
+                "lines_marked": float((mk != 0).mean()),
+                "mark_bits_per_marked_line": float(np.array([bin(int(v)).count("1") for v in mk[mk != 0][:100000]]).mean())
+                if (mk != 0).any() else 0.0,
+            }
         out["homes"][mode] = {
+            "query_windows_absent": float((~present).mean()),
+            "marks": variants,
             "lines_per_present_key": float(lines_present.mean()),
             "present_keys_past_first_line": float((lines_present > 1).mean()),
             "longest_chain_lines": int(lines_present.max()),
@@ -174,7 +260,15 @@ def main():
     for mode, m in r["homes"].items():
         print(f"{mode}:")
         for k, v in m.items():
-            print(f"  {k:36s} {v:.4f}" if isinstance(v, float) else f"  {k:36s} {v}")
+            if k != "marks":
+                print(f"  {k:36s} {v:.4f}" if isinstance(v, float) else f"  {k:36s} {v}")
+        print(f"  overflow marks ({m['marks']['16']['lines_marked']:.2%} of lines are full and were passed, "
+              f"{m['full_lines']:.2%} are full):")
+        print("    bits  lines/window  past first line  absent-key lines  requests/window (instruction / tile merge)")
+        for bits, v in m["marks"].items():
+            print(f"    {bits:>4s}  {v['query_lines_per_window']:12.4f}  {v['query_windows_past_first_line']:15.2%}  "
+                  f"{v['lines_per_absent_key']:16.4f}  {v['query_requests_per_window']:.4f} / "
+                  f"{v['query_requests_per_window_tile_merge']:.4f}")
 
 
 if __name__ == "__main__":
