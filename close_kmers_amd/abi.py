@@ -83,6 +83,14 @@ class SigStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SigPass(ctypes.Structure):
+    """kgx_sig_pass: the keys lo_key <= raw_key < hi_key and what they held."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("lo_key", "hi_key", "n_tuples", "n_sets", "n_kept")]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RollupResult(ctypes.Structure):
     _fields_ = [("n_seq", ctypes.c_uint32), ("offsets", ctypes.c_void_p), ("rows", ctypes.c_void_p),
                 ("n_events", ctypes.c_uint64)]
@@ -299,6 +307,9 @@ SIGNATURES = {
     "kgx_svc_stop": (_INT, [_P]),
     "kgx_svc_stat": (_INT, [_P, _CS, ctypes.POINTER(_U64)]),
     "kgx_sig_select": (_INT, [_INT, _P, _P, _P, _U32, _U32, _PP]),
+    "kgx_sig_select_passes": (_INT, [_INT, _P, _P, _P, _U32, _U32, _U64, _PP]),
+    "kgx_sig_pass_count": (_INT, [_P, ctypes.POINTER(_U32)]),
+    "kgx_sig_pass_get": (_INT, [_P, _U32, ctypes.POINTER(SigPass)]),
     "kgx_sig_stats_get": (_INT, [_P, ctypes.POINTER(SigStats)]),
     "kgx_sig_records": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
     "kgx_sig_image": (_INT, [_P, _U64, _PP, ctypes.POINTER(_U64)]),
@@ -538,10 +549,13 @@ class Image:
 
 class Signatures:
     """Signature k-mers selected on the device from function-labelled proteins
-    (kgx_sig_select): seq_function[i] is the function index of sequence i, or
-    negative for a sequence that takes no part."""
+    (kgx_sig_select_passes): seq_function[i] is the function index of sequence
+    i, or negative for a sequence that takes no part.  max_pass_tuples bounds
+    the tuples held on the device at once (the selection then runs in passes
+    over key ranges, with the same records); 0 = what the device holds."""
 
-    def __init__(self, residues, offsets, seq_function, n_functions: int, device: int = 0):
+    def __init__(self, residues, offsets, seq_function, n_functions: int, device: int = 0, *,
+                 max_pass_tuples: int = 0):
         residues = np.ascontiguousarray(np.frombuffer(bytes(residues), np.uint8)
                                         if isinstance(residues, (bytes, bytearray)) else residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -549,10 +563,24 @@ class Signatures:
         if len(offsets) != len(fn) + 1:
             raise ValueError("offsets holds one entry more than seq_function")
         h = ctypes.c_void_p()
-        check(lib().kgx_sig_select(device, residues.ctypes.data if residues.size else None, offsets.ctypes.data,
-                                   fn.ctypes.data if fn.size else None, len(fn), n_functions, ctypes.byref(h)),
-              "kgx_sig_select")
+        if not 0 <= max_pass_tuples < 1 << 64:
+            raise ValueError("max_pass_tuples is an unsigned 64-bit count")
+        check(lib().kgx_sig_select_passes(device, residues.ctypes.data if residues.size else None,
+                                          offsets.ctypes.data, fn.ctypes.data if fn.size else None, len(fn),
+                                          n_functions, max_pass_tuples, ctypes.byref(h)),
+              "kgx_sig_select_passes")
         self.handle = h.value
+
+    def passes(self) -> list[dict]:
+        """The passes that held a tuple, in key order: lo_key, hi_key, n_tuples, n_sets, n_kept."""
+        n = _U32()
+        check(lib().kgx_sig_pass_count(self.handle, ctypes.byref(n)), "kgx_sig_pass_count")
+        out = []
+        for i in range(n.value):
+            p = SigPass()
+            check(lib().kgx_sig_pass_get(self.handle, i, ctypes.byref(p)), "kgx_sig_pass_get")
+            out.append(p.as_dict())
+        return out
 
     def stats(self) -> dict:
         s = SigStats()

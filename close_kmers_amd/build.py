@@ -34,7 +34,7 @@ LIB_SOURCES = ["kgx_lookup.hip", "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.h
                "kgx_runtime.cpp",
                "kgx_host_batch.cpp", "kgx_pool.cpp", "kgx_svc.cpp", "kguts_hip.cpp", "kgx_handlers.cpp"]
 HEADERS = ["kgx_internal.h", "kgx_device.h", "kgx_line_home.h", "kguts_hip.h", "kgx_rt.h", "kgx_lstd.h", "kgx_handlers.h",
-           "kgx_wave_sort.h", "kgx_options.h", "kgx_dispatch.h", "kgx_score_map.h"]
+           "kgx_wave_sort.h", "kgx_options.h", "kgx_dispatch.h", "kgx_score_map.h", "kgx_sig_plan.h"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{CSRC}",
           "-Wall", "-Wno-unused-function"]
 

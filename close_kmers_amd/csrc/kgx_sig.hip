@@ -5,10 +5,17 @@
  *                process_set :663-710, compute_weight_of_signature :841-853,
  *                write_hashtable :860-898).  DESIGN.md §8.8 states the rules.
  *
+ *   passes    a corpus of more tuples than one pass may hold (max_pass_tuples)
+ *             is selected in passes over ascending, disjoint ranges of raw
+ *             key, planned on the host (kgx_sig_plan.h) from counts of the
+ *             windows by their leading letters (count: as emit walks them,
+ *             1,600 bins per workgroup in LDS).  Every stage below up to the
+ *             records runs per pass; NSF, KS and the weights follow the last
  *   emit      one thread per residue position; the 8 bytes of its window are
- *             checked against a 256-byte LDS table (the 40 letters of
- *             ok_prot) and valid windows of labelled sequences are written,
- *             compacted, as {raw key (8 bytes big-endian), n << 32 | sequence}
+ *             checked against a 256-byte LDS table (the ranks of the 40
+ *             letters of ok_prot) and valid windows of labelled sequences
+ *             whose key lies in the pass's range are written, compacted, as
+ *             {raw key (8 bytes big-endian), n << 32 | sequence}
  *   order     two stable hipCUB radix sorts: by n, then by raw key -- a set
  *             (all tuples of one key) is contiguous and ordered by offset,
  *             so its median is one read
@@ -30,6 +37,7 @@
 #include "kgx.h"
 #include "kgx_device.h"
 #include "kgx_rt.h"
+#include "kgx_sig_plan.h"
 
 namespace kgx {
 
@@ -52,10 +60,6 @@ static uint64_t builder_num_sigs(uint64_t n_kept)
     return 0;
 }
 
-/* ok_prot (build_signature_kmers.cc:569-570): the 20 residues in both cases
- * (clearing bit 5 maps 'a'..'z' onto 'A'..'Z' and nothing else onto them) */
-__device__ __forceinline__ bool sig_letter_ok(uint32_t c) { return residue_code(c & ~0x20u) < 20u; }
-
 /* ---- emit ---------------------------------------------------------------- */
 
 /* the sequence holding residue position g, given off[lo] <= g < off[hi]:
@@ -73,43 +77,79 @@ __device__ __forceinline__ uint32_t seq_of(const uint64_t *__restrict__ off, uin
     return lo;
 }
 
+/* byte -> rank among the 40 letters of ok_prot in ascending byte order (the
+ * 20 residues, then the same in lower case: clearing bit 5 maps 'a'..'z' onto
+ * 'A'..'Z' and nothing else onto them), kSigNoRank for every other byte: the
+ * device's form of sig_rank_table (kgx_sig_plan.h) */
+__device__ __forceinline__ uint8_t sig_rank(uint32_t c)
+{
+    const uint32_t r = residue_code(c & ~0x20u);
+    return r < 20u ? (uint8_t)(r + ((c & 0x20u) ? 20u : 0u)) : kSigNoRank;
+}
+
+/* What emit and count share: a tile of 256 residue positions and each
+ * thread's window of it. */
+struct SigTile {
+    uint8_t rank[256];
+    uint8_t tile[256 + 8];
+    uint32_t tile_seq[2]; /* the sequences of the tile's first and last position */
+};
+
+__device__ __forceinline__ void sig_tile_init(SigTile &sh) { sh.rank[threadIdx.x] = sig_rank(threadIdx.x); }
+
+/* Loads the tile at g0 and decides thread t's window, at position g0 + t: a
+ * tuple iff it lies in a labelled sequence and its 8 bytes are letters.
+ * Every thread of the workgroup calls it; it starts with a barrier (the table
+ * on the first round, the last round's tile after). */
+__device__ __forceinline__ bool sig_tile_window(SigTile &sh, const uint8_t *__restrict__ res, uint64_t total,
+                                                const uint64_t *__restrict__ off, uint32_t n_seq,
+                                                const int32_t *__restrict__ seq_fn, uint64_t g0, uint64_t &key,
+                                                uint64_t &val)
+{
+    const uint32_t t = threadIdx.x;
+    __syncthreads();
+    for (uint32_t i = t; i < 256 + 8; i += 256)
+        sh.tile[i] = g0 + i < total ? res[g0 + i] : 0;
+    /* two searches of the whole offset array per tile; the threads then search between them */
+    if (t == 0 || t == 255)
+        sh.tile_seq[t >> 7] = seq_of(off, 0, n_seq, std::min(g0 + t, total - 1));
+    __syncthreads();
+    const uint64_t g = g0 + t;
+    bool valid = false;
+    key = 0;
+    val = 0;
+    if (g < total) {
+        const uint32_t s = seq_of(off, sh.tile_seq[0], sh.tile_seq[1] + 1, g);
+        const uint64_t end = off[s + 1];
+        if (seq_fn[s] >= 0 && g + 8 <= end) {
+            valid = true;
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t c = sh.tile[t + j];
+                valid = valid && sh.rank[c] != kSigNoRank;
+                key = key << 8 | c;
+            }
+            val = (end - g) << 32 | s;
+        }
+    }
+    return valid;
+}
+
+/* the tuples with lo <= key < hi, compacted */
 __global__ __launch_bounds__(256) void sig_emit_kernel(const uint8_t *__restrict__ res, uint64_t total,
                                                        const uint64_t *__restrict__ off, uint32_t n_seq,
-                                                       const int32_t *__restrict__ seq_fn, uint64_t *keys,
-                                                       uint64_t *vals, uint64_t cap, unsigned long long *n_out)
+                                                       const int32_t *__restrict__ seq_fn, uint64_t lo, uint64_t hi,
+                                                       uint64_t *keys, uint64_t *vals, uint64_t cap,
+                                                       unsigned long long *n_out)
 {
-    __shared__ uint8_t ok[256];
-    __shared__ uint8_t tile[256 + 8];
+    __shared__ SigTile sh;
     __shared__ uint32_t wave_n[4];
-    __shared__ uint32_t tile_seq[2]; /* the sequences of the tile's first and last position */
     __shared__ unsigned long long block_base;
     const uint32_t t = threadIdx.x;
-    ok[t] = sig_letter_ok(t) ? 1 : 0;
+    sig_tile_init(sh);
     for (uint64_t g0 = (uint64_t)blockIdx.x * 256; g0 < total; g0 += (uint64_t)gridDim.x * 256) {
-        __syncthreads(); /* the table on the first round, the last round's tile after */
-        for (uint32_t i = t; i < 256 + 8; i += 256)
-            tile[i] = g0 + i < total ? res[g0 + i] : 0;
-        /* two searches of the whole offset array per tile; the threads then search between them */
-        if (t == 0 || t == 255)
-            tile_seq[t >> 7] = seq_of(off, 0, n_seq, std::min(g0 + t, total - 1));
-        __syncthreads();
-        const uint64_t g = g0 + t;
-        bool valid = false;
-        uint64_t key = 0, val = 0;
-        if (g < total) {
-            const uint32_t s = seq_of(off, tile_seq[0], tile_seq[1] + 1, g);
-            const uint64_t end = off[s + 1];
-            if (seq_fn[s] >= 0 && g + 8 <= end) {
-                valid = true;
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j++) {
-                    const uint32_t c = tile[t + j];
-                    valid = valid && ok[c];
-                    key = key << 8 | c;
-                }
-                val = (end - g) << 32 | s;
-            }
-        }
+        uint64_t key, val;
+        const bool valid = sig_tile_window(sh, res, total, off, n_seq, seq_fn, g0, key, val) && key >= lo && key < hi;
         const uint64_t m = __ballot(valid);
         if (lane_id() == 0)
             wave_n[t >> 6] = (uint32_t)__popcll(m);
@@ -125,6 +165,37 @@ __global__ __launch_bounds__(256) void sig_emit_kernel(const uint8_t *__restrict
             vals[j] = val;
         }
     }
+}
+
+/* Planning: among the tuples whose key starts with the d letters of `prefix`
+ * (its top d bytes), how many continue with each pair of letters.  The 1,600
+ * bins are the workgroup's own in LDS; a window costs one LDS atomic and no
+ * global one, and the workgroup adds its non-zero bins to `bins` once, after
+ * its last tile. */
+__global__ __launch_bounds__(256) void sig_count_kernel(const uint8_t *__restrict__ res, uint64_t total,
+                                                        const uint64_t *__restrict__ off, uint32_t n_seq,
+                                                        const int32_t *__restrict__ seq_fn, uint64_t prefix,
+                                                        uint32_t d, unsigned long long *bins)
+{
+    __shared__ SigTile sh;
+    __shared__ uint32_t hist[kSigBins]; /* a workgroup sees fewer than 2^32 positions */
+    const uint32_t t = threadIdx.x;
+    sig_tile_init(sh);
+    for (uint32_t i = t; i < kSigBins; i += 256)
+        hist[i] = 0;
+    const uint32_t rest = 64 - 8 * d; /* d <= 6: the bits below the prefix */
+    for (uint64_t g0 = (uint64_t)blockIdx.x * 256; g0 < total; g0 += (uint64_t)gridDim.x * 256) {
+        uint64_t key, val;
+        const bool valid = sig_tile_window(sh, res, total, off, n_seq, seq_fn, g0, key, val);
+        if (valid && (d == 0 || (key ^ prefix) >> rest == 0)) {
+            const uint32_t a = sh.rank[(key >> (rest - 8)) & 0xFFu], b = sh.rank[(key >> (rest - 16)) & 0xFFu];
+            atomicAdd(&hist[a * kSigRanks + b], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kSigBins; i += 256)
+        if (hist[i])
+            atomicAdd(&bins[i], (unsigned long long)hist[i]);
 }
 
 /* ---- sets ------------------------------------------------------------------ */
@@ -349,6 +420,11 @@ __device__ __forceinline__ float sig_weight(float NSF, float KS, float NSi, floa
     return (float)(a + log((double)q));
 }
 
+/* The records of one pass's kept sets.  kFinal: the pass is the only one, NSF
+ * and KS (= n_kept) are known, and the weights and the storable count are
+ * taken here.  Otherwise both wait for sig_weights_kernel after the last
+ * pass, and function_wt is left 0. */
+template <bool kFinal>
 __global__ __launch_bounds__(256) void sig_records_kernel(const uint32_t *__restrict__ kept, uint32_t n_kept,
                                                           const uint32_t *__restrict__ starts,
                                                           const uint64_t *__restrict__ keys,
@@ -366,28 +442,52 @@ __global__ __launch_bounds__(256) void sig_records_kernel(const uint32_t *__rest
         o.n_tuples = cnt;
         o.n_best = sets.n_best[s];
         o.median_offset = (int32_t)(vals[b + cnt / 2] >> 32);
-        o.function_wt = sig_weight(NSF, (float)n_kept, (float)cnt, (float)n_fn[o.function_index], (float)o.n_best);
+        o.function_wt = 0.0f;
+        if (kFinal)
+            o.function_wt =
+                sig_weight(NSF, (float)n_kept, (float)cnt, (float)n_fn[o.function_index], (float)o.n_best);
         recs[r] = o;
         reinterpret_cast<uint32_t *>(recs + r)[9] = 0; /* the struct's tail padding: no stale bytes reach the host */
         storable += o.code <= MAX_ENCODED;
     }
+    if (!kFinal)
+        return;
     storable = sum_wave(storable); /* one add per wave: same-address atomics serialise */
     if (lane_id() == 0 && storable)
         atomicAdd(n_storable, (unsigned long long)storable);
 }
 
-/* the records as the insert's entry arrays */
-__global__ void sig_entries_kernel(const kgx_sig_record *__restrict__ recs, uint32_t n, uint64_t *keys, int32_t *fi,
-                                   int32_t *otu, uint16_t *avg, float *wt)
+/* after the last of several passes: the weights of n records (one pass's
+ * share of the KS kept ones) and the storable among them */
+__global__ __launch_bounds__(256) void sig_weights_kernel(kgx_sig_record *recs, uint64_t n,
+                                                          const uint32_t *__restrict__ n_fn, float NSF, float KS,
+                                                          unsigned long long *n_storable)
 {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t storable = 0; /* a thread sees fewer than 2^32 records */
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+        const kgx_sig_record o = recs[r];
+        recs[r].function_wt =
+            sig_weight(NSF, KS, (float)o.n_tuples, (float)n_fn[o.function_index], (float)o.n_best);
+        storable += o.code <= MAX_ENCODED;
+    }
+    storable = sum_wave(storable);
+    if (lane_id() == 0 && storable)
+        atomicAdd(n_storable, (unsigned long long)storable);
+}
+
+/* n records as the insert's entry arrays, from entry `base` on */
+__global__ void sig_entries_kernel(const kgx_sig_record *__restrict__ recs, uint64_t n, uint64_t base, uint64_t *keys,
+                                   int32_t *fi, int32_t *otu, uint16_t *avg, float *wt)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n)
         return;
-    keys[r] = recs[r].code;
-    fi[r] = recs[r].function_index;
-    otu[r] = -1;
-    avg[r] = (uint16_t)recs[r].median_offset; /* truncates, as insert_kmer's unsigned short parameter */
-    wt[r] = recs[r].function_wt;
+    const uint64_t e = base + r;
+    keys[e] = recs[r].code;
+    fi[e] = recs[r].function_index;
+    otu[e] = -1;
+    avg[e] = (uint16_t)recs[r].median_offset; /* truncates, as insert_kmer's unsigned short parameter */
+    wt[e] = recs[r].function_wt;
 }
 
 static inline dim3 sig_grid(uint64_t n, uint32_t per_block = 256, uint32_t cap = 8192)
@@ -401,10 +501,17 @@ using namespace kgx;
 
 static_assert(sizeof(kgx_sig_record) == 40, "kgx_sig_record: 36 bytes of fields, 4 of tail padding");
 
+static_assert(sizeof(kgx_sig_record) == kSigRecordBytes, "the budget counts 40 bytes per record");
+
 struct kgx_sig {
     int device = -1;
     kgx_sig_stats stats{};
-    DevBuf recs; /* stats.n_kept kgx_sig_record, ascending raw_key */
+    /* the stats.n_kept records in ascending raw_key order: the kept sets of
+     * pass i, recs[i] of them (fewer than 2^31), are chunk[i].  A pass's
+     * records are allocated when their number is known, so nothing is ever
+     * copied to make room and the records take 40 bytes each, no more. */
+    std::vector<DevBuf> chunk;
+    std::vector<kgx_sig_pass> passes; /* those that held a tuple; chunk[i] belongs to passes[i] */
     std::vector<kgx_sig_record> host;
     bool host_valid = false;
     float stage_ms[kSigStages] = {};
@@ -421,75 +528,106 @@ struct kgx_sig {
 
 namespace {
 
-struct Events {
-    hipEvent_t e[kSigStages + 1] = {};
-    int n = 0;
-    ~Events()
+enum { kUpload = 0, kEmit, kOrder, kSegment, kRecords };
+
+/* stage times: the time between two marks goes to the stage the later one
+ * names, summed over the passes */
+struct StageClock {
+    std::vector<hipEvent_t> e; /* e[0] starts the next lap */
+    std::vector<int> stage;    /* stage[i]: of the lap that ends at e[i] */
+    float *ms;
+    explicit StageClock(float *out) : ms(out) {}
+    StageClock(const StageClock &) = delete;
+    ~StageClock()
     {
-        for (int i = 0; i < n; i++)
-            (void)hipEventDestroy(e[i]);
+        for (hipEvent_t x : e)
+            (void)hipEventDestroy(x);
     }
-    int mark()
+    int mark(int s)
     {
-        HIP_TRY(hipEventCreate(&e[n]));
-        n++;
-        HIP_TRY(hipEventRecord(e[n - 1], nullptr));
+        hipEvent_t x;
+        HIP_TRY(hipEventCreate(&x));
+        e.push_back(x);
+        stage.push_back(s);
+        HIP_TRY(hipEventRecord(x, nullptr));
+        return KGX_OK;
+    }
+    /* adds the laps marked so far; the last mark starts the next lap */
+    int flush()
+    {
+        if (e.empty())
+            return KGX_OK;
+        HIP_TRY(hipEventSynchronize(e.back()));
+        for (size_t i = 1; i < e.size(); i++) {
+            float t = 0;
+            HIP_TRY(hipEventElapsedTime(&t, e[i - 1], e[i]));
+            ms[stage[i]] += t;
+        }
+        for (size_t i = 0; i + 1 < e.size(); i++)
+            (void)hipEventDestroy(e[i]);
+        e.erase(e.begin(), e.end() - 1);
+        stage.erase(stage.begin(), stage.end() - 1);
         return KGX_OK;
     }
 };
 
-int sig_select(kgx_sig *S, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
-               uint32_t n_seq, const std::vector<uint32_t> &n_fn, uint64_t cap, uint32_t max_len)
-{
-    const uint64_t base = seq_offsets[0], total = seq_offsets[n_seq] - base;
-    kgx_sig_stats &st = S->stats;
-    st.n_windows = cap;
-    st.num_sigs_rule = builder_num_sigs(0);
-    if (cap == 0)
-        return KGX_OK;
-    Events ev;
-    int rc = ev.mark();
-    if (rc)
-        return rc;
+/* one selection: what lives across its passes */
+struct SigRun {
+    kgx_sig *S;
+    uint64_t total = 0; /* residues */
+    uint32_t n_seq = 0, max_len = 0, n_words = 0;
+    DevBuf res, off, fn, nfn, cnt, bins, bitmap; /* the corpus, the counters, the planner's bins, NSF's bits */
+    DevBuf kA, vA, kB, vB, tmp, best, nbest, keep, lists, kept; /* a pass's; they grow to the largest pass */
+    StageClock clock;
+    explicit SigRun(kgx_sig *s) : S(s), clock(s->stage_ms) {}
+    /* cnt: tuples, NSF, storable | the two list lengths */
+    unsigned long long *n_tup() const { return cnt.as<unsigned long long>(); }
+    unsigned long long *n_sf() const { return n_tup() + 1; }
+    unsigned long long *n_stor() const { return n_tup() + 2; }
+    uint32_t *n_lists() const { return reinterpret_cast<uint32_t *>(n_tup() + 3); }
+};
 
-    /* upload: residues, offsets from 0, functions, sequences per function */
-    DevBuf d_res, d_off, d_fn, d_nfn, d_cnt;
-    SIG_ALLOC(d_res, total);
-    SIG_ALLOC(d_off, ((uint64_t)n_seq + 1) * 8);
-    SIG_ALLOC(d_fn, (uint64_t)n_seq * 4);
-    SIG_ALLOC(d_nfn, std::max<uint64_t>(n_fn.size(), 1) * 4);
-    SIG_ALLOC(d_cnt, 4 * 8); /* tuples, NSF, storable | the two list lengths */
-    {
-        std::vector<uint64_t> off0(n_seq + 1);
-        for (uint32_t i = 0; i <= n_seq; i++)
-            off0[i] = seq_offsets[i] - base;
-        HIP_TRY(hipMemcpy(d_off.p, off0.data(), off0.size() * 8, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(d_res.p, residues + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_fn.p, seq_function, (uint64_t)n_seq * 4, hipMemcpyHostToDevice));
-    if (!n_fn.empty())
-        HIP_TRY(hipMemcpy(d_nfn.p, n_fn.data(), n_fn.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_cnt.p, 0, 4 * 8));
-    unsigned long long *d_ntup = d_cnt.as<unsigned long long>(), *d_nsf = d_ntup + 1, *d_nstor = d_ntup + 2;
-    uint32_t *d_nlists = reinterpret_cast<uint32_t *>(d_ntup + 3);
-    if ((rc = ev.mark()))
-        return rc;
+/* the planner's counter on the device: one launch per call */
+int sig_count(SigRun &R, uint64_t prefix, int d, uint64_t *counts)
+{
+    HIP_TRY(hipMemset(R.bins.p, 0, kSigBins * 8));
+    hipLaunchKernelGGL(sig_count_kernel, sig_grid(R.total, 256, 2048), dim3(256), 0, nullptr, R.res.as<uint8_t>(),
+                       R.total, R.off.as<uint64_t>(), R.n_seq, R.fn.as<int32_t>(), prefix, (uint32_t)d,
+                       R.bins.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(counts, R.bins.p, kSigBins * 8, hipMemcpyDeviceToHost));
+    return KGX_OK;
+}
+
+/* One pass: the tuples with lo <= key < hi through emit, order, segment and
+ * records.  cap: room for its tuples -- their exact number when the pass was
+ * planned.  only: there is no other pass, so NSF and KS are this pass's and
+ * its records are final; otherwise the weights wait for the last pass. */
+int sig_pass(SigRun &R, uint64_t lo, uint64_t hi, uint64_t cap, bool planned, bool last, bool only)
+{
+    kgx_sig_stats &st = R.S->stats;
+    int rc;
+    HIP_TRY(hipMemset(R.cnt.p, 0, 4 * 8));
 
     /* emit */
-    DevBuf kA, vA, kB, vB;
-    SIG_ALLOC(kA, cap * 8);
-    SIG_ALLOC(vA, cap * 8);
-    hipLaunchKernelGGL(sig_emit_kernel, sig_grid(total), dim3(256), 0, nullptr, d_res.as<uint8_t>(), total,
-                       d_off.as<uint64_t>(), n_seq, d_fn.as<int32_t>(), kA.as<uint64_t>(), vA.as<uint64_t>(), cap,
-                       d_ntup);
+    SIG_ALLOC(R.kA, cap * 8);
+    SIG_ALLOC(R.vA, cap * 8);
+    DevBuf &kA = R.kA, &vA = R.vA, &kB = R.kB, &vB = R.vB, &tmp = R.tmp;
+    hipLaunchKernelGGL(sig_emit_kernel, sig_grid(R.total), dim3(256), 0, nullptr, R.res.as<uint8_t>(), R.total,
+                       R.off.as<uint64_t>(), R.n_seq, R.fn.as<int32_t>(), lo, hi, kA.as<uint64_t>(), vA.as<uint64_t>(),
+                       cap, R.n_tup());
     HIP_TRY(hipGetLastError());
     unsigned long long T = 0;
-    HIP_TRY(hipMemcpy(&T, d_ntup, 8, hipMemcpyDeviceToHost));
-    if (T > cap)
+    HIP_TRY(hipMemcpy(&T, R.n_tup(), 8, hipMemcpyDeviceToHost));
+    if (T > cap && !planned)
         return fail(KGX_EDEVICE, "signature selection: more tuples than windows");
-    st.n_tuples = T;
-    d_res.release();
-    if ((rc = ev.mark()))
+    if (planned && T != cap)
+        return fail(KGX_EDEVICE, "signature selection: a pass planned for " + std::to_string(cap) + " tuples emitted " +
+                                     std::to_string(T));
+    st.n_tuples += T;
+    if (last)
+        R.res.release();
+    if ((rc = R.clock.mark(kEmit)))
         return rc;
     if (T == 0)
         return KGX_OK;
@@ -498,9 +636,8 @@ int sig_select(kgx_sig *S, const char *residues, const uint64_t *seq_offsets, co
     SIG_ALLOC(kB, T * 8);
     SIG_ALLOC(vB, T * 8);
     int n_bits = 1;
-    while (n_bits < 32 && (max_len >> n_bits))
+    while (n_bits < 32 && (R.max_len >> n_bits))
         n_bits++;
-    DevBuf tmp;
     size_t tb1 = 0, tb2 = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, vA.as<uint64_t>(), vB.as<uint64_t>(), kA.as<uint64_t>(),
                                                kB.as<uint64_t>(), (int)T, 32, 32 + n_bits, nullptr));
@@ -511,13 +648,13 @@ int sig_select(kgx_sig *S, const char *residues, const uint64_t *seq_offsets, co
                                                kB.as<uint64_t>(), (int)T, 32, 32 + n_bits, nullptr));
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb2, kB.as<uint64_t>(), kA.as<uint64_t>(), vB.as<uint64_t>(),
                                                vA.as<uint64_t>(), (int)T, 0, 64, nullptr));
-    if ((rc = ev.mark()))
+    if ((rc = R.clock.mark(kOrder)))
         return rc;
 
     /* sets: heads -> starts (kB / vB are scratch from here) */
     uint8_t *head = vB.as<uint8_t>();        /* T bytes of T * 8 */
     uint32_t *starts = kB.as<uint32_t>();    /* n_sets + 1 <= T + 1 words of 2 * T */
-    unsigned long long *d_nsel = d_nsf;      /* borrowed until the popcount */
+    unsigned long long *d_nsel = R.n_sf();   /* borrowed until the popcount */
     hipLaunchKernelGGL(sig_heads_kernel, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, nullptr,
                        kA.as<uint64_t>(), (uint32_t)T, head);
     hipcub::CountingInputIterator<uint32_t> ids(0);
@@ -532,68 +669,161 @@ int sig_select(kgx_sig *S, const char *residues, const uint64_t *seq_offsets, co
     const uint32_t t32 = (uint32_t)T;
     HIP_TRY(hipMemcpy(starts + n_sets, &t32, 4, hipMemcpyHostToDevice)); /* T == 1: word 1 of kB's 2 */
     HIP_TRY(hipMemset(d_nsel, 0, 8));
-    st.n_sets = n_sets;
+    st.n_sets += n_sets;
 
     /* segment */
-    DevBuf best, nbest, keep, lists, bitmap, kept;
-    SIG_ALLOC(best, n_sets * 4);
-    SIG_ALLOC(nbest, n_sets * 4);
-    SIG_ALLOC(keep, n_sets);
+    SIG_ALLOC(R.best, n_sets * 4);
+    SIG_ALLOC(R.nbest, n_sets * 4);
+    SIG_ALLOC(R.keep, n_sets);
     /* a listed set holds more than kSmallSet tuples */
     const uint64_t list_cap = T / (kSmallSet + 1) + 1, block_cap = T / (kWaveSet + 1) + 1;
-    SIG_ALLOC(lists, (list_cap + block_cap) * 4);
-    const uint32_t n_words = (n_seq + 31) / 32;
-    SIG_ALLOC(bitmap, (uint64_t)n_words * 4);
-    HIP_TRY(hipMemset(bitmap.p, 0, (uint64_t)n_words * 4));
-    const SetOut so{best.as<int32_t>(), nbest.as<uint32_t>(), keep.as<uint8_t>()};
-    uint32_t *wave_list = lists.as<uint32_t>(), *block_list = wave_list + list_cap;
+    SIG_ALLOC(R.lists, (list_cap + block_cap) * 4);
+    const SetOut so{R.best.as<int32_t>(), R.nbest.as<uint32_t>(), R.keep.as<uint8_t>()};
+    uint32_t *wave_list = R.lists.as<uint32_t>(), *block_list = wave_list + list_cap;
+    uint32_t *bitmap = R.bitmap.as<uint32_t>();
     hipLaunchKernelGGL(sig_small_kernel, sig_grid(n_sets), dim3(256), 0, nullptr, starts, (uint32_t)n_sets,
-                       vA.as<uint64_t>(), d_fn.as<int32_t>(), so, bitmap.as<uint32_t>(), wave_list, block_list,
-                       d_nlists);
+                       vA.as<uint64_t>(), R.fn.as<int32_t>(), so, bitmap, wave_list, block_list, R.n_lists());
     hipLaunchKernelGGL(sig_wave_kernel, sig_grid(list_cap, 4, 2048), dim3(256), 0, nullptr, starts, wave_list,
-                       d_nlists, vA.as<uint64_t>(), d_fn.as<int32_t>(), so, bitmap.as<uint32_t>());
+                       R.n_lists(), vA.as<uint64_t>(), R.fn.as<int32_t>(), so, bitmap);
     hipLaunchKernelGGL(sig_block_kernel, sig_grid(block_cap, 1, 2048), dim3(256), 0, nullptr, starts, block_list,
-                       d_nlists + 1, vA.as<uint64_t>(), d_fn.as<int32_t>(), so, bitmap.as<uint32_t>());
+                       R.n_lists() + 1, vA.as<uint64_t>(), R.fn.as<int32_t>(), so, bitmap);
     HIP_TRY(hipGetLastError());
-    if ((rc = ev.mark()))
+    if ((rc = R.clock.mark(kSegment)))
         return rc;
 
-    /* NSF, the kept sets in set order, their records */
-    hipLaunchKernelGGL(sig_popcount_kernel, sig_grid(n_words, 256, 1024), dim3(256), 0, nullptr,
-                       bitmap.as<uint32_t>(), n_words, d_nsf);
+    /* the kept sets in set order and their records; of the only pass with NSF, hence final */
+    if (only)
+        hipLaunchKernelGGL(sig_popcount_kernel, sig_grid(R.n_words, 256, 1024), dim3(256), 0, nullptr, bitmap,
+                           R.n_words, R.n_sf());
     const uint64_t kept_bytes = (n_sets * 4 + 7) & ~7ull; /* the ids, then their count */
-    SIG_ALLOC(kept, kept_bytes + 8);
-    unsigned long long *d_nkept = reinterpret_cast<unsigned long long *>(kept.as<uint8_t>() + kept_bytes);
+    SIG_ALLOC(R.kept, kept_bytes + 8);
+    unsigned long long *d_nkept = reinterpret_cast<unsigned long long *>(R.kept.as<uint8_t>() + kept_bytes);
     tb = 0;
-    HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, keep.as<uint8_t>(), kept.as<uint32_t>(), d_nkept,
+    HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, R.keep.as<uint8_t>(), R.kept.as<uint32_t>(), d_nkept,
                                           (int)n_sets, nullptr));
     SIG_ALLOC(tmp, tb);
-    HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, ids, keep.as<uint8_t>(), kept.as<uint32_t>(), d_nkept,
+    HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, ids, R.keep.as<uint8_t>(), R.kept.as<uint32_t>(), d_nkept,
                                           (int)n_sets, nullptr));
     unsigned long long n_kept = 0, nsf = 0;
     HIP_TRY(hipMemcpy(&n_kept, d_nkept, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&nsf, d_nsf, 8, hipMemcpyDeviceToHost));
+    if (only)
+        HIP_TRY(hipMemcpy(&nsf, R.n_sf(), 8, hipMemcpyDeviceToHost));
     if (n_kept > n_sets)
         return fail(KGX_EDEVICE, "signature selection: bad kept count");
-    st.n_kept = n_kept;
-    st.n_seqs_with_signature = nsf;
-    st.num_sigs_rule = builder_num_sigs(n_kept);
+    st.n_kept += n_kept;
+    DevBuf recs;
     if (n_kept) {
-        SIG_ALLOC(S->recs, n_kept * sizeof(kgx_sig_record));
-        hipLaunchKernelGGL(sig_records_kernel, sig_grid(n_kept), dim3(256), 0, nullptr, kept.as<uint32_t>(),
-                           (uint32_t)n_kept, starts, kA.as<uint64_t>(), vA.as<uint64_t>(), so, d_nfn.as<uint32_t>(),
-                           (float)nsf, S->recs.as<kgx_sig_record>(), d_nstor);
+        SIG_ALLOC(recs, n_kept * sizeof(kgx_sig_record));
+        const auto records = only ? sig_records_kernel<true> : sig_records_kernel<false>;
+        hipLaunchKernelGGL(records, sig_grid(n_kept), dim3(256), 0, nullptr, R.kept.as<uint32_t>(), (uint32_t)n_kept,
+                           starts, kA.as<uint64_t>(), vA.as<uint64_t>(), so, R.nfn.as<uint32_t>(), (float)nsf,
+                           recs.as<kgx_sig_record>(), R.n_stor());
         HIP_TRY(hipGetLastError());
-        unsigned long long n_stor = 0;
-        HIP_TRY(hipMemcpy(&n_stor, d_nstor, 8, hipMemcpyDeviceToHost));
-        st.n_storable = n_stor;
     }
-    if ((rc = ev.mark()))
+    if (only) {
+        unsigned long long n_stor = 0;
+        HIP_TRY(hipMemcpy(&n_stor, R.n_stor(), 8, hipMemcpyDeviceToHost));
+        st.n_storable = n_stor;
+        st.n_seqs_with_signature = nsf;
+    }
+    R.S->chunk.push_back(std::move(recs));
+    R.S->passes.push_back(kgx_sig_pass{lo, hi, T, n_sets, n_kept});
+    if ((rc = R.clock.mark(kRecords)))
         return rc;
-    HIP_TRY(hipEventSynchronize(ev.e[ev.n - 1]));
-    for (int i = 0; i + 1 < ev.n && i < kSigStages; i++)
-        HIP_TRY(hipEventElapsedTime(&S->stage_ms[i], ev.e[i], ev.e[i + 1]));
-    return KGX_OK;
+    return R.clock.flush();
+}
+
+int sig_select(kgx_sig *S, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
+               uint32_t n_seq, const std::vector<uint32_t> &n_fn, uint64_t cap, uint32_t max_len, uint64_t budget)
+{
+    const uint64_t base = seq_offsets[0], total = seq_offsets[n_seq] - base;
+    kgx_sig_stats &st = S->stats;
+    st.n_windows = cap;
+    st.num_sigs_rule = builder_num_sigs(0);
+    if (cap == 0)
+        return KGX_OK;
+    SigRun R(S);
+    R.total = total;
+    R.n_seq = n_seq;
+    R.max_len = max_len;
+    R.n_words = (n_seq + 31) / 32;
+    int rc = R.clock.mark(kUpload);
+    if (rc)
+        return rc;
+
+    /* upload: residues, offsets from 0, functions, sequences per function */
+    SIG_ALLOC(R.res, total);
+    SIG_ALLOC(R.off, ((uint64_t)n_seq + 1) * 8);
+    SIG_ALLOC(R.fn, (uint64_t)n_seq * 4);
+    SIG_ALLOC(R.nfn, std::max<uint64_t>(n_fn.size(), 1) * 4);
+    SIG_ALLOC(R.cnt, 4 * 8);
+    SIG_ALLOC(R.bitmap, (uint64_t)R.n_words * 4);
+    {
+        std::vector<uint64_t> off0(n_seq + 1);
+        for (uint32_t i = 0; i <= n_seq; i++)
+            off0[i] = seq_offsets[i] - base;
+        HIP_TRY(hipMemcpy(R.off.p, off0.data(), off0.size() * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(R.res.p, residues + base, total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R.fn.p, seq_function, (uint64_t)n_seq * 4, hipMemcpyHostToDevice));
+    if (!n_fn.empty())
+        HIP_TRY(hipMemcpy(R.nfn.p, n_fn.data(), n_fn.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(R.bitmap.p, 0, (uint64_t)R.n_words * 4));
+    if (budget == 0) {
+        size_t free_bytes = 0, all_bytes = 0;
+        HIP_TRY(hipMemGetInfo(&free_bytes, &all_bytes));
+        budget = sig_auto_budget(free_bytes, cap);
+    }
+    if ((rc = R.clock.mark(kUpload)))
+        return rc;
+
+    /* within the budget: one pass over every key, nothing counted */
+    if (cap <= budget)
+        return sig_pass(R, 0, kSigAllKeys, cap, false, true, true);
+
+    /* the passes, planned from counts on the device (timed as emit) */
+    std::vector<SigPass> plan;
+    SIG_ALLOC(R.bins, kSigBins * 8);
+    SigPlanner planner(budget, [&R](uint64_t prefix, int d, uint64_t *counts) { return sig_count(R, prefix, d, counts); });
+    if ((rc = planner.plan(&plan)))
+        return rc == KGX_ERANGE && !planner.error().empty() ? fail(rc, planner.error()) : rc;
+    if (plan.empty()) { /* no tuple anywhere */
+        if ((rc = R.clock.mark(kEmit)))
+            return rc;
+        return R.clock.flush();
+    }
+    uint64_t largest = 0;
+    for (const SigPass &p : plan)
+        largest = std::max(largest, p.n_tuples);
+    SIG_ALLOC(R.kA, largest * 8);
+    SIG_ALLOC(R.vA, largest * 8);
+    SIG_ALLOC(R.kB, largest * 8);
+    SIG_ALLOC(R.vB, largest * 8);
+    const bool only = plan.size() == 1;
+    for (size_t i = 0; i < plan.size(); i++)
+        if ((rc = sig_pass(R, plan[i].lo_key, plan[i].hi_key, plan[i].n_tuples, true, i + 1 == plan.size(), only)))
+            return rc;
+    if (only)
+        return KGX_OK;
+
+    /* NSF and KS are whole: the weights */
+    hipLaunchKernelGGL(sig_popcount_kernel, sig_grid(R.n_words, 256, 1024), dim3(256), 0, nullptr,
+                       R.bitmap.as<uint32_t>(), R.n_words, R.n_sf());
+    HIP_TRY(hipGetLastError());
+    unsigned long long nsf = 0, n_stor = 0;
+    HIP_TRY(hipMemcpy(&nsf, R.n_sf(), 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < S->chunk.size(); i++)
+        if (S->passes[i].n_kept)
+            hipLaunchKernelGGL(sig_weights_kernel, sig_grid(S->passes[i].n_kept), dim3(256), 0, nullptr,
+                               S->chunk[i].as<kgx_sig_record>(), S->passes[i].n_kept, R.nfn.as<uint32_t>(),
+                               (float)nsf, (float)st.n_kept, R.n_stor());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&n_stor, R.n_stor(), 8, hipMemcpyDeviceToHost));
+    st.n_storable = n_stor;
+    st.n_seqs_with_signature = nsf;
+    if ((rc = R.clock.mark(kRecords)))
+        return rc;
+    return R.clock.flush();
 }
 
 }  // namespace
@@ -603,9 +833,17 @@ extern "C" {
 int kgx_sig_select(int device, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
                    uint32_t n_seq, uint32_t n_functions, kgx_sig **out)
 {
+    return kgx_sig_select_passes(device, residues, seq_offsets, seq_function, n_seq, n_functions, 0, out);
+}
+
+int kgx_sig_select_passes(int device, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
+                          uint32_t n_seq, uint32_t n_functions, uint64_t max_pass_tuples, kgx_sig **out)
+{
     if (!out || !seq_offsets || (n_seq && !seq_function))
         return fail(KGX_EINVAL, "null argument");
     *out = nullptr;
+    if (max_pass_tuples > kSigMaxPassTuples) /* hipCUB counts items in an int */
+        return fail(KGX_EINVAL, "max_pass_tuples = " + std::to_string(max_pass_tuples) + " is above 2^31-1");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
         return fail(KGX_EDEVICE, "no such HIP device " + std::to_string(device));
@@ -632,17 +870,35 @@ int kgx_sig_select(int device, const char *residues, const uint64_t *seq_offsets
     }
     if (cap && !residues)
         return fail(KGX_EINVAL, "null residues");
-    if (cap > 0x7FFFFFFFull) /* hipCUB counts items in an int; chunking is out of scope */
-        return fail(KGX_ERANGE, "more than 2^31-1 windows in one corpus");
     HIP_TRY(hipSetDevice(device));
     kgx_sig *S = new kgx_sig;
     S->device = device;
-    const int rc = sig_select(S, residues, seq_offsets, seq_function, n_seq, n_fn, cap, (uint32_t)max_len);
+    const int rc = sig_select(S, residues, seq_offsets, seq_function, n_seq, n_fn, cap, (uint32_t)max_len,
+                              max_pass_tuples);
     if (rc) {
         delete S;
         return rc;
     }
+    S->stats.num_sigs_rule = builder_num_sigs(S->stats.n_kept);
     *out = S;
+    return KGX_OK;
+}
+
+int kgx_sig_pass_count(const kgx_sig *s, uint32_t *n)
+{
+    if (!s || !n)
+        return fail(KGX_EINVAL, "null argument");
+    *n = (uint32_t)s->passes.size();
+    return KGX_OK;
+}
+
+int kgx_sig_pass_get(const kgx_sig *s, uint32_t i, kgx_sig_pass *out)
+{
+    if (!s || !out)
+        return fail(KGX_EINVAL, "null argument");
+    if (i >= s->passes.size())
+        return fail(KGX_ERANGE, "pass " + std::to_string(i) + " of " + std::to_string(s->passes.size()));
+    *out = s->passes[i];
     return KGX_OK;
 }
 
@@ -669,9 +925,11 @@ int kgx_sig_records(kgx_sig *s, const kgx_sig_record **recs, uint64_t *n)
     if (!s->host_valid) {
         HIP_TRY(hipSetDevice(s->device));
         s->host.resize(s->stats.n_kept);
-        if (s->stats.n_kept)
-            HIP_TRY(hipMemcpy(s->host.data(), s->recs.p, s->stats.n_kept * sizeof(kgx_sig_record),
-                              hipMemcpyDeviceToHost));
+        uint64_t at = 0;
+        for (size_t i = 0; i < s->chunk.size(); at += s->passes[i++].n_kept)
+            if (s->passes[i].n_kept)
+                HIP_TRY(hipMemcpy(s->host.data() + at, s->chunk[i].p, s->passes[i].n_kept * sizeof(kgx_sig_record),
+                                  hipMemcpyDeviceToHost));
         s->host_valid = true;
     }
     *recs = s->host.data();
@@ -698,9 +956,13 @@ int kgx_sig_image(kgx_sig *s, uint64_t num_sigs, kgx_image **out, uint64_t *n_st
     SIG_ALLOC(otu, m * 4);
     SIG_ALLOC(avg, m * 2);
     SIG_ALLOC(wt, m * 4);
-    if (n) {
-        hipLaunchKernelGGL(sig_entries_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr,
-                           s->recs.as<kgx_sig_record>(), (uint32_t)n, keys.as<uint64_t>(), fi.as<int32_t>(),
+    uint64_t at = 0;
+    for (size_t i = 0; i < s->chunk.size(); at += s->passes[i++].n_kept) {
+        const uint64_t c = s->passes[i].n_kept; /* a pass's: fewer than 2^31 */
+        if (!c)
+            continue;
+        hipLaunchKernelGGL(sig_entries_kernel, dim3((uint32_t)((c + 255) / 256)), dim3(256), 0, nullptr,
+                           s->chunk[i].as<kgx_sig_record>(), c, at, keys.as<uint64_t>(), fi.as<int32_t>(),
                            otu.as<int32_t>(), avg.as<uint16_t>(), wt.as<float>());
         HIP_TRY(hipGetLastError());
     }

@@ -23,7 +23,12 @@ and functions or genome names taken from FASTA definition lines (the
 "[genome]" regex); a function here is exactly the definitions' second column.
 
     python -m close_kmers_amd.signatures --definitions defs.tsv [more.tsv ...] \\
-        --fasta genome1.fa genome2.fa ... [--min-reps 5] [--keep-function NAME ...] --out DIR
+        --fasta genome1.fa genome2.fa ... [--min-reps 5] [--keep-function NAME ...] --out DIR \\
+        [--max-pass-tuples N]
+
+A corpus whose tuples do not fit the device at once is selected in passes over
+key ranges with the same result; --max-pass-tuples bounds a
+pass by hand, and the printed statistics say how many passes ran (n_passes).
 """
 from __future__ import annotations
 
@@ -112,21 +117,23 @@ def write_indexes(out_dir: str, functions: list[bytes]) -> None:
 
 
 def build_data_dir(definitions, fastas, out_dir: str, min_reps: int = 5, keep=(), device: int = 0,
-                   num_sigs: int = 0) -> dict:
+                   num_sigs: int = 0, max_pass_tuples: int = 0) -> dict:
     """Runs the whole builder on `device`; returns the selection's statistics
-    with n_functions and n_stored added."""
+    with n_functions, n_stored and n_passes added.  max_pass_tuples: the most
+    tuples one pass of the selection holds (0: what the device holds)."""
     from . import abi
     id_function = read_definitions(definitions)
     records = [read_fasta(p) for p in fastas]
     functions = kept_functions(id_function, [[rid for rid, _ in recs] for recs in records], min_reps, keep)
     res, off, fn = label(id_function, records, functions)
     write_indexes(out_dir, functions)
-    with abi.Signatures(res, off, fn, len(functions), device) as sig:
+    with abi.Signatures(res, off, fn, len(functions), device, max_pass_tuples=max_pass_tuples) as sig:
         stats = sig.stats()
+        n_passes = len(sig.passes())
         img, stored = sig.image(num_sigs)
         with img:
             img.save(out_dir)
-    stats.update(n_functions=len(functions), n_stored=stored)
+    stats.update(n_functions=len(functions), n_stored=stored, n_passes=n_passes)
     return stats
 
 
@@ -139,8 +146,11 @@ def main(argv=None) -> int:
     ap.add_argument("--out", required=True, help="kmer data directory to write")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--num-sigs", type=int, default=0, help="table size (default: the builder's prime rule)")
+    ap.add_argument("--max-pass-tuples", type=int, default=0,
+                    help="most tuples held on the device at once (default: what it holds, at most 2^31-1)")
     a = ap.parse_args(argv)
-    stats = build_data_dir(a.definitions, a.fasta, a.out, a.min_reps, a.keep_function, a.device, a.num_sigs)
+    stats = build_data_dir(a.definitions, a.fasta, a.out, a.min_reps, a.keep_function, a.device, a.num_sigs,
+                           a.max_pass_tuples)
     print(json.dumps(stats))
     return 0
 

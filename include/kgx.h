@@ -367,12 +367,32 @@ typedef struct kgx_sig_stats {
 } kgx_sig_stats;
 /* residues / seq_offsets as in kgx_process_batch; seq_function[i] is the
  * function of sequence i, or negative for none (the sequence contributes
- * nothing); a value >= n_functions is KGX_ERANGE, as are a sequence longer
- * than 2^31-1 and a corpus of more than 2^31-1 windows.  The whole corpus is
- * held in HBM in one pass (about 50 bytes per window): KGX_ENOMEM when it
- * does not fit.  KGX_EDEVICE without a gfx950 device: there is no CPU path. */
+ * nothing); a value >= n_functions is KGX_ERANGE, as is a sequence longer
+ * than 2^31-1.  The residues (1 byte per window) and the kept records (40
+ * bytes each) are held in HBM; the tuples go through it in passes over
+ * ascending, disjoint ranges of raw_key, each of at most max_pass_tuples
+ * tuples (about 62 bytes per tuple of the largest pass).  max_pass_tuples 0 =
+ * the smaller of 2^31-1 and what the device's free memory holds; above 2^31-1
+ * it is KGX_EINVAL.  A corpus of at most max_pass_tuples windows is one pass.
+ * A set is never split: one k-mer with more tuples than max_pass_tuples is
+ * KGX_ERANGE (kgx_last_error names it).  The records, weights included, do
+ * not depend on the passes.  KGX_ENOMEM when the residues, the largest pass
+ * or the records do not fit.  KGX_EDEVICE without a gfx950 device: there is
+ * no CPU path. */
+int kgx_sig_select_passes(int device, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
+                          uint32_t n_seq, uint32_t n_functions, uint64_t max_pass_tuples, kgx_sig **out);
+/* kgx_sig_select_passes with max_pass_tuples 0 */
 int kgx_sig_select(int device, const char *residues, const uint64_t *seq_offsets, const int32_t *seq_function,
                    uint32_t n_seq, uint32_t n_functions, kgx_sig **out);
+/* the passes of the selection that held a tuple, in key order.  A pass that
+ * was planned covers lo_key <= raw_key < hi_key; the single pass of a corpus
+ * within the budget is not planned and reports lo_key 0, hi_key 2^64-1. */
+typedef struct kgx_sig_pass {
+    uint64_t lo_key, hi_key;
+    uint64_t n_tuples, n_sets, n_kept;
+} kgx_sig_pass;
+int kgx_sig_pass_count(const kgx_sig *s, uint32_t *n);
+int kgx_sig_pass_get(const kgx_sig *s, uint32_t i, kgx_sig_pass *out);
 int kgx_sig_stats_get(const kgx_sig *s, kgx_sig_stats *out);
 /* host view of the kept records in ascending raw_key order, valid until
  * kgx_sig_destroy */
@@ -381,9 +401,10 @@ int kgx_sig_records(kgx_sig *s, const kgx_sig_record **recs, uint64_t *n);
  * (uint16_t)median_offset), inserted on the device as kgx_image_build
  * inserts; num_sigs 0 = the builder's rule.  KGX_EFULL as kgx_image_build. */
 int kgx_sig_image(kgx_sig *s, uint64_t num_sigs, kgx_image **out, uint64_t *n_stored);
-/* device time of the last selection's stages, in ms: upload, emit, order
- * (the two sorts), segment (set heads, vote, keep test, bitmap), records
- * (popcount, compaction, weights) */
+/* device time of the last selection's stages, in ms, summed over its passes:
+ * upload, emit (with the planner's count launches), order (the two sorts),
+ * segment (set heads, vote, keep test, bitmap), records (popcount,
+ * compaction, weights) */
 #define KGX_SIG_STAGES 5
 int kgx_sig_stage_ms(const kgx_sig *s, float *ms);
 int kgx_sig_destroy(kgx_sig *s);

@@ -1,12 +1,14 @@
 """Signature selection benchmark: labelled proteins -> kept k-mers -> image.
 
     python tools/bench_signatures.py [--n-prot 100000] [--fam-size 10] [--reps 3] [--no-cpu-baseline]
+        [--max-pass-tuples N]
 
 Corpus: n_prot proteins of 300 aa in families of fam_size -- each family is
 one source protein of synth.py's generator with 10% substitutions per member
 -- labelled with their family as function.  Timed on the device: one
 kgx_sig_select call from host buffers (wall clock, the best of --reps) with
-its per-stage event times (upload, emit, order, segment, records), and the
+its per-stage event times (upload, emit, order, segment, records; summed over
+the passes when --max-pass-tuples makes it run in several), and the
 image build from the selected records.  Beside it, the same rules on one CPU
 thread (tools/sig_cpu_restate.cpp: std::sort of the tuples, then a walk over
 the sets), built here; its counts must equal the device's.  Prints one JSON
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--fam-size", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--max-pass-tuples", type=int, default=0, help="most tuples per pass (0: what the device holds)")
     args = ap.parse_args()
 
     from close_kmers_amd import abi
@@ -70,10 +73,10 @@ def main():
     t_image = stored = None
     for rep in range(args.reps + 1):  # the first pass warms the runtime up
         t0 = time.perf_counter()
-        sig = abi.Signatures(res, off, fn, n_fn)
+        sig = abi.Signatures(res, off, fn, n_fn, max_pass_tuples=args.max_pass_tuples)
         dt = time.perf_counter() - t0
         if rep and (best is None or dt < best):
-            best, stages, stats = dt, sig.stage_ms(), sig.stats()
+            best, stages, stats, n_passes = dt, sig.stage_ms(), sig.stats(), len(sig.passes())
         if rep == args.reps:
             recs = sig.records()
             t0 = time.perf_counter()
@@ -84,7 +87,8 @@ def main():
     out = {"metric": "signature_tuples_per_s", "value": stats["n_tuples"] / best, "unit": "tuples/s",
            "n_prot": len(fn), "n_functions": n_fn, "residues": int(res.size), "select_ms": best * 1e3,
            "stage_ms": {k: round(v, 3) for k, v in stages.items()}, "device_ms": round(sum(stages.values()), 3),
-           "image_ms": t_image * 1e3, "n_stored": stored, **stats}
+           "image_ms": t_image * 1e3, "n_stored": stored, "max_pass_tuples": args.max_pass_tuples,
+           "n_passes": n_passes, **stats}
     if not args.no_cpu_baseline:
         o = np.zeros(6, np.uint64)
         wsum = ctypes.c_double()
