@@ -72,18 +72,57 @@ KGX_HD uint32_t mix32(uint32_t x)
     return x;
 }
 
-/* the home line of `key` (<= 20^8) among n_lines, magic = mod_magic(n_lines) */
-KGX_HD uint64_t line_home(uint64_t key, uint64_t n_lines, uint64_t magic, uint32_t mode)
+/* The two 7-mers of a window from its eight residue codes c[0..7] (each below
+ * 20): a = key / 20, b = key mod 20^7, for key the big-endian base-20 number
+ * the probes encode as ka * 160000 + kb, ka and kb its two 4-mers.  A probe
+ * that has the codes takes the 7-mers from them instead of dividing them back
+ * out of the key; both are below 2^31 and every factor is below 2^24. */
+KGX_HD void seven_mers(const uint32_t *c, uint32_t &a, uint32_t &b)
 {
-    if (mode == LINE_HOME_MOD)
-        return mod_by(key, n_lines, magic);
-    const uint32_t a = (uint32_t)(key / 20u), b = (uint32_t)(key % 1280000000ull); /* 7-mers: below 2^31 */
+    const uint32_t ka = ((c[0] * 20 + c[1]) * 20 + c[2]) * 20 + c[3];
+    const uint32_t kb = ((c[4] * 20 + c[5]) * 20 + c[6]) * 20 + c[7];
+    a = ka * 8000u + (c[4] * 20 + c[5]) * 20 + c[6];
+    b = (ka - c[0] * 8000u) * 160000u + kb;
+}
+
+/* the minimizer home of the key whose 7-mers are a and b */
+KGX_HD uint64_t minimizer_home(uint32_t a, uint32_t b, uint64_t n_lines, uint64_t magic)
+{
     const uint32_t ha = mix32(a), hb = mix32(b);
     const uint32_t m = ha <= hb ? a : b, hm = ha <= hb ? ha : hb;
     /* 35 bits, the most mod_by takes: a second hash of the minimizer (hm
      * itself leans low, being a minimum) over three low bits of the first */
     const uint64_t x = (uint64_t)mix32(m ^ 0x85EBCA6Bu) << 3 | (hm & 7u);
     return mod_by(x, n_lines, magic);
+}
+
+/* the home line of `key` (<= 20^8) among n_lines, magic = mod_magic(n_lines) */
+KGX_HD uint64_t line_home(uint64_t key, uint64_t n_lines, uint64_t magic, uint32_t mode)
+{
+    if (mode == LINE_HOME_MOD)
+        return mod_by(key, n_lines, magic);
+    const uint32_t a = (uint32_t)(key / 20u), b = (uint32_t)(key % 1280000000ull); /* 7-mers: below 2^31 */
+    return minimizer_home(a, b, n_lines, magic);
+}
+
+/* the same home for a caller that holds the key's 7-mers (seven_mers): no
+ * 64-bit division (the key is 20 a + the last residue, b mod 20) */
+KGX_HD uint64_t line_home_7mers(uint32_t a, uint32_t b, uint64_t n_lines, uint64_t magic, uint32_t mode)
+{
+    if (mode == LINE_HOME_MOD)
+        return mod_by((uint64_t)a * 20u + b % 20u, n_lines, magic);
+    return minimizer_home(a, b, n_lines, magic);
+}
+
+/* Whether a probe table of num_sigs buckets under the launchers' home word
+ * is an aligned index: whole 4-record lines, line-aligned homes, overflow
+ * marks (below), and few enough lines that a line number, and the n_lines + 2
+ * lines a chain may visit, fit 32 bits.  The line probe's aligned slice body
+ * holds for exactly these tables; every other one runs the generic kernel. */
+KGX_HD bool line_index_aligned(uint64_t num_sigs, uint32_t home)
+{
+    return home_marks_of(home) && home_shift_of(home) == 2 && num_sigs >= 4 && num_sigs % 4 == 0 &&
+           num_sigs / 4 <= 0xFFFFFFFFull - 2;
 }
 
 /* the home bucket of `key` in a probe table of num_sigs buckets; `home` as

@@ -508,7 +508,8 @@ __device__ __forceinline__ void encode_tile(const uint8_t *__restrict__ residues
                                             const uint64_t *__restrict__ wbase, uint32_t s,
                                             uint64_t W, uint64_t g0, uint32_t lane,
                                             const uint8_t *code_tab, uint64_t *key, bool *ok,
-                                            uint32_t *pos, uint32_t *sq)
+                                            uint32_t *pos, uint32_t *sq, uint32_t *a7 = nullptr,
+                                            uint32_t *b7 = nullptr)
 {
     /* byte offsets from residues - bm, which is 4-aligned */
     const uint64_t bm = reinterpret_cast<uintptr_t>(residues) & 3;
@@ -562,6 +563,10 @@ __device__ __forceinline__ void encode_tile(const uint8_t *__restrict__ residues
         const uint32_t ka = ((c0 * 20 + c1) * 20 + c2) * 20 + c3;
         const uint32_t kb = ((c4 * 20 + c5) * 20 + c6) * 20 + c7;
         key[j] = (uint64_t)ka * 160000u + kb;
+        if (a7) { /* the key's two 7-mers, for the home (kgx_line_home.h) */
+            const uint32_t cc[8] = {c0, c1, c2, c3, c4, c5, c6, c7};
+            seven_mers(cc, a7[j], b7[j]);
+        }
     }
 }
 
@@ -586,7 +591,7 @@ __device__ __forceinline__ void encode_tile_dna(const uint8_t *__restrict__ base
                                                 const uint64_t *__restrict__ wbase, uint32_t s, uint64_t W,
                                                 uint64_t g0, uint32_t lane, const uint8_t *cls_tab,
                                                 const uint8_t *cod_tab, uint64_t *key, bool *ok, uint32_t *pos,
-                                                uint32_t *sq)
+                                                uint32_t *sq, uint32_t *a7 = nullptr, uint32_t *b7 = nullptr)
 {
     const uint64_t bm = reinterpret_cast<uintptr_t>(bases) & 3;
     uint64_t wb_lo = wbase[s], wb_hi = wbase[s + 1], an = anchor[s];
@@ -662,6 +667,8 @@ __device__ __forceinline__ void encode_tile_dna(const uint8_t *__restrict__ base
         const uint32_t ka = ((c[0] * 20 + c[1]) * 20 + c[2]) * 20 + c[3];
         const uint32_t kb = ((c[4] * 20 + c[5]) * 20 + c[6]) * 20 + c[7];
         key[j] = (uint64_t)ka * 160000u + kb;
+        if (a7)
+            seven_mers(c, a7[j], b7[j]);
     }
 }
 
@@ -837,7 +844,95 @@ __global__ __launch_bounds__(256) void probe_kernel(
  * is a miss (the reference spins forever there; probe_kernel stops after
  * num_sigs buckets -- same answer, since every bucket has been seen).
  * The matching lane writes the record to LDS for the window's owner.
+ *
+ * probe_slice_aligned is one 64-window slice of it over an aligned index
+ * (line_index_aligned, kgx_line_home.h: whole 4-record lines, line-aligned
+ * homes, overflow marks, fewer than 2^32 - 2 lines).  The chain rules are
+ * those of the kernel's generic slice; what the alignment settles is left
+ * out: a chain's position is a 32-bit line number, every record of a line
+ * belongs to the chain and lies inside the table, and a line searched in vain
+ * was searched whole, so its overflow mark for the key decides whether the
+ * chain goes on.  The owner lane hands its quad three words per instruction: the
+ * key's low word, a word with key bits 32-34, the open-chain bit and
+ * line_mark of the key, and the home line.  Each lane keeps, per instruction,
+ * the key's high bits and the one bit of its own record's last dword that
+ * holds the key's mark (or none) in one word: bits 0-2 and 28-31 do not meet.
+ * `rec` and `hitf` are the slice's 64 hand-over slots in LDS.
  */
+__device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ packed, uint32_t n_lines, uint64_t key,
+                                                    bool ok, uint32_t home_line, uint32_t q, uint32_t c, uint4 *rec,
+                                                    uint8_t *hitf)
+{
+    constexpr uint32_t G = 4, NQ = 64 / G;
+    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+    constexpr uint32_t MAX_HI = (uint32_t)(MAX_ENCODED >> 32), MAX_LO = (uint32_t)MAX_ENCODED;
+    static_assert(KEY_HI == 7u && (MARK_BITS_W & KEY_HI) == 0, "key bits 32-34 beside the mark bit");
+    const uint32_t own = (uint32_t)(key >> 32) | (uint32_t)ok << 3 | line_mark(key) << 4;
+    uint32_t klo[G], kw[G], ln[G];
+    uint32_t live = 0; /* bit i: instruction i's chain is still open */
+#pragma unroll
+    for (int i = 0; i < (int)G; i++) {
+        const int owner = (int)(NQ * i + q);
+        klo[i] = (uint32_t)__shfl((int)(uint32_t)key, owner);
+        ln[i] = (uint32_t)__shfl((int)home_line, owner);
+        const uint32_t o = (uint32_t)__shfl((int)own, owner);
+        live |= (o >> 3 & 1u) << i;
+        const uint32_t g = o >> 4;
+        kw[i] = (o & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+    }
+    const uint32_t cbit = 1u << c, upto = (2u << c) - 1u; /* this lane's record of its line; it and those before */
+    constexpr uint32_t MARKED = 1u << G;
+    const uint32_t max_lines = n_lines + 2; /* lines a chain may visit before it has covered the table */
+    for (uint32_t round = 0;; round++) {
+        /* only open chains load; d is fresh each round (no merge with an
+         * older value at the branch join, so no wait for the load there) */
+        uint4 d[G];
+#pragma unroll
+        for (int i = 0; i < (int)G; i++)
+            if (live >> i & 1u)
+                d[i] = packed[(uint64_t)ln[i] * G + c];
+        uint32_t hitm = 0; /* bit i: this lane's record is instruction i's hit */
+#pragma unroll
+        for (int i = 0; i < (int)G; i++) {
+            /* The record's key is tested in its two words, and for equality
+             * through xor: after `d.x == klo` the compiler hands over klo in
+             * d.x's place, and after a 64-bit compare it builds a register
+             * pair in the loaded one's; either way the record is put together
+             * again by copies that wait for the load at the branch join. */
+            const uint32_t kh = d[i].y & KEY_HI;
+            const uint32_t diff = (d[i].x ^ klo[i]) | ((d[i].y ^ kw[i]) & KEY_HI); /* 0: the key */
+            const bool ends = diff == 0 || kh > MAX_HI || (kh == MAX_HI && d[i].x > MAX_LO); /* or > MAX_ENCODED */
+            /* the line's word, ORed over the quad by two DPP moves (a quad
+             * is the lanes of one line, and every lane of the wave is active
+             * here): bit c, record c holds the key or is empty; MARKED, the
+             * line carries the key's mark.  0 for a closed chain. */
+            uint32_t w = (ends ? cbit : 0u) | ((d[i].w & kw[i]) >= 1u << 28 ? MARKED : 0u);
+            w = live >> i & 1u ? w : 0u;
+            w |= (uint32_t)xor_lane((int32_t)w, 1);
+            w |= (uint32_t)xor_lane((int32_t)w, 2);
+            /* the line's first match or empty bucket ends the chain; a match
+             * there is the hit */
+            hitm |= diff == 0 && (w & upto) == cbit ? 1u << i : 0u;
+            /* on: nothing found, and the key's mark set (a full line whose
+             * mark for the key is clear was never passed by it) */
+            live = (w & (2u * MARKED - 1)) == MARKED ? live : live & ~(1u << i);
+            ln[i] = ln[i] + 1 == n_lines ? 0 : ln[i] + 1;
+        }
+        /* the hits are handed to the windows' owners after all four tests:
+         * no branch stands between the tests, so their instructions mix */
+#pragma unroll
+        for (int i = 0; i < (int)G; i++)
+            if (hitm >> i & 1u) {
+                rec[NQ * i + q] = d[i];
+                hitf[NQ * i + q] = 1;
+            }
+        if (round + 1 >= max_lines) /* the table covered */
+            live = 0;
+        if (!__any(live != 0))
+            break;
+    }
+}
+
 template <int J, int G, bool DNA, bool MARKS>
 __global__ __launch_bounds__(256) void probe_line_kernel(
     const uint8_t *__restrict__ residues, uint64_t n_residues, const uint64_t *__restrict__ seq_off,
@@ -875,6 +970,33 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
     uint64_t key[J];
     uint32_t pos[J], sq[J];
     bool ok[J];
+    const uint32_t q = lane / G, c = lane % G;
+    /* MARKS: the table is an aligned index (the launcher: line_index_aligned,
+     * G = 4).  Its homes come from the 7-mers the encode holds and its slices
+     * run probe_slice_aligned; without, the kernel is the generic one below
+     * and holds none of the aligned body's instructions or registers */
+    static_assert(!MARKS || G == 4, "the index's lines are 4 records");
+    if constexpr (MARKS) {
+        uint32_t a7[J], b7[J];
+        if (DNA)
+            encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab,
+                               cod_tab, key, ok, pos, sq, a7, b7);
+        else
+            encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
+                           pos, sq, a7, b7);
+        const uint32_t n_lines = (uint32_t)(num_sigs / G);
+        uint32_t home_line[J];
+#pragma unroll
+        for (int j = 0; j < J; j++) {
+            home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(hs)) : 0;
+            lds_hit[wave][64 * j + lane] = 0;
+        }
+        /* one 64-window slice at a time, as below */
+#pragma unroll
+        for (int j = 0; j < J; j++)
+            probe_slice_aligned(packed, n_lines, key[j], ok[j], home_line[j], q, c, &lds_rec[wave][64 * j],
+                                &lds_hit[wave][64 * j]);
+    } else {
     if (DNA)
         encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, cod_tab,
                            key, ok, pos, sq);
@@ -888,12 +1010,6 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
         lds_hit[wave][64 * j + lane] = 0;
     }
 
-    const uint32_t q = lane / G, c = lane % G;
-    /* MARKS: the table is a line index with overflow marks (the launcher
-     * picks it only for G = 4 with whole 4-record lines and line-aligned
-     * homes, so a line searched in vain was searched whole); without, the
-     * kernel holds none of the mark test's instructions or registers */
-    static_assert(!MARKS || G == 4, "the index's lines are 4 records");
     /* lines a chain may visit before it has covered the whole table */
     const uint64_t max_lines = num_sigs / G + 2;
     /* One 64-window slice (G instructions) at a time, each with its own
@@ -905,11 +1021,9 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
 #pragma unroll
     for (int j = 0; j < J; j++) {
     uint64_t K[G], cur[G];
-    /* bit i: instruction i's chain is still open.  With overflow marks the
-     * owner also hands on line_mark of its key */
+    /* bit i: instruction i's chain is still open */
     uint32_t live = 0;
-    const uint32_t own = MARKS ? (uint32_t)ok[j] | line_mark(key[j]) << 8 : (uint32_t)ok[j];
-    uint32_t mbit[MARKS ? G : 1]; /* this lane's bit of its record's last dword, if it holds the key's mark */
+    const uint32_t own = (uint32_t)ok[j];
 #pragma unroll
     for (int i = 0; i < G; i++) {
         const uint32_t owner = NQ * i + q;
@@ -917,8 +1031,6 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
         cur[i] = __shfl(home[j], (int)owner);
         const uint32_t o = (uint32_t)__shfl((int)own, (int)owner);
         live |= (o & 1u) << i;
-        if constexpr (MARKS)
-            mbit[i] = c == mark_record(o >> 8) ? 1u << mark_bit_w(o >> 8) : 0u;
     }
     for (uint64_t round = 0;; round++) {
         /* only open chains load; d is fresh each round (no merge with an
@@ -942,14 +1054,6 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
             const uint64_t me = __ballot(valid && kb > MAX_ENCODED);
             const uint32_t gm = (uint32_t)(mm >> (G * q)) & ((1u << G) - 1);
             const uint32_t ge = (uint32_t)(me >> (G * q)) & ((1u << G) - 1);
-            /* the line's overflow mark for K[i]: the lane holding record
-             * mark >> 2 tests its bit.  A full line searched in vain whose
-             * mark for the key is clear was never passed by it: a miss. */
-            bool passed = true;
-            if constexpr (MARKS) {
-                const uint64_t mk = __ballot(valid && (d[i].w & mbit[i]));
-                passed = ((uint32_t)(mk >> (G * q)) & ((1u << G) - 1)) != 0;
-            }
             if (act) {
                 const uint32_t ev = gm | ge;
                 if (ev) {
@@ -960,7 +1064,7 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
                         lds_hit[wave][w] = 1;
                     }
                     live &= ~(1u << i);
-                } else if (round + 1 >= max_lines || !passed) {
+                } else if (round + 1 >= max_lines) {
                     live &= ~(1u << i);
                 } else {
                     cur[i] = line + G >= num_sigs ? 0 : line + G;
@@ -972,6 +1076,7 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
             break;
     }
     } /* slices */
+    } /* generic */
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -993,13 +1098,12 @@ static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *resi
                               uint32_t n_seq, const void *table, uint64_t num_sigs, uint32_t hs, uint4 *hot,
                               uint4 *cold, uint64_t *hit_mask, uint32_t dyn_lds, uint32_t nt = 0)
 {
-    /* the kernel with the mark test only over an index that has marks: whole
-     * 4-record lines and line-aligned homes; every other table runs the
-     * kernel without it */
-    const bool marks = G == 4 && home_marks_of(hs) && home_shift_of(hs) == 2 && num_sigs % 4 == 0;
+    /* the aligned slice body, with the mark test, only over an aligned index
+     * (kgx_line_home.h); every other table runs the generic kernel, which
+     * ignores marks and stays exact */
     auto *kernel = probe_line_kernel<J, G, DNA, false>;
     if constexpr (G == 4)
-        if (marks)
+        if (line_index_aligned(num_sigs, hs))
             kernel = probe_line_kernel<J, G, DNA, true>;
     hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues, n_residues, seq_off, wbase,
                        tile_seq, n_seq, static_cast<const uint4 *>(table), num_sigs,
