@@ -216,6 +216,7 @@ SIGNATURES = {
     "kgx_image_set_line_index": (_INT, [_P, _U32]),
     "kgx_image_line_count": (_U64, [_P]),
     "kgx_image_line_home": (_U32, [_P]),
+    "kgx_image_line_twins": (_U64, [_P]),
     "kgx_image_line_stats": (_INT, [_P, ctypes.POINTER(_U64)]),
     "kgx_image_set_filter": (_INT, [_P, _INT]),
     "kgx_image_download": (_INT, [_P, _P, _U64]),
@@ -487,6 +488,11 @@ class Image:
     def line_home(self) -> int:
         """the KGX_LINE_HOME mode the line index was built with (0 mod, 1 minimizer)"""
         return lib().kgx_image_line_home(self.handle)
+
+    @property
+    def line_twins(self) -> int:
+        """twin records in the line index (KGX_LINE_TWINS): the keys stored under two home lines"""
+        return lib().kgx_image_line_twins(self.handle)
 
     LINE_STATS = ("stored", "past_home", "full_lines", "marked_lines", "mark_bits", "missing", "unjustified",
                   "reserved")

@@ -189,14 +189,17 @@ hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long l
 /* the line index of a PACKED16 table (lines_build_kernel): 4 * n_lines
  * buckets, homes by line_home(home_mode); *overflow |= 1 when some record
  * found no bucket; marks: then the overflow marks of kgx_line_home.h, by
- * lines_mark_kernel */
+ * lines_mark_kernel; twins (minimizer home with marks only): every key with
+ * two home lines is stored under both, *n_twins += those second records */
 hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t home_mode, bool marks, uint32_t *overflow, hipStream_t stream);
-/* kgx_image_line_stats: stats[0..7) += stored records, records past their
- * home line, full lines, lines with a mark, mark bits set, missing and
- * unjustified marks; scratch: (n_lines + 1) / 2 zeroed words */
-hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, uint32_t *scratch,
-                              unsigned long long *stats, hipStream_t stream);
+                              uint32_t home_mode, bool marks, bool twins, uint32_t *overflow,
+                              unsigned long long *n_twins, hipStream_t stream);
+/* kgx_image_line_stats: stats[0..7) += stored keys, records past their
+ * home line (both twice over an index with twins, see lines_mark_kernel),
+ * full lines, lines with a mark, mark bits set, missing and unjustified
+ * marks; scratch: (n_lines + 1) / 2 zeroed words */
+hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, bool twins,
+                              uint32_t *scratch, unsigned long long *stats, hipStream_t stream);
 /* AoS -> packed; *not_packable |= 1 when some stored bucket does not fit */
 hipError_t launch_pack(const kgx_sig_kmer *table, packed_bucket *packed, uint64_t n,
                        uint32_t *not_packable, hipStream_t stream);

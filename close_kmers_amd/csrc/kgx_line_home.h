@@ -16,6 +16,25 @@
  *     their home line whenever the 7-mer they share is the minimizer of both:
  *     it has the smallest hash of three, probability 1/3, present or absent.
  *     A 7-mer lies in two windows only, so no more than two in a row share.
+ *
+ * Twin records (HOME_TWINS_BIT, built only over LINE_HOME_MINIMIZER with
+ * overflow marks).  The builder inserts every key a second time, walking from
+ * the home of its other 7-mer (twin_home), unless both 7-mers are homed on
+ * one line; each copy goes to the first empty bucket of its walk, whether or
+ * not the walk passes the other copy, so a key with two home lines always
+ * has exactly two records.  A key is then found from either of its 7-mers'
+ * homes, and the aligned line probe needs no minimum: the window with an even
+ * index in its batch starts at the home of its last seven residues and the
+ * odd window after it at the home of its first seven, which are the same
+ * 7-mer (pair_home), so the two always ask for one line.  A prober that
+ * starts at the minimizer home finds the same records as before: the copy
+ * that home's walk placed, or the twin where it lies earlier on the chain.
+ * The two copies differ in mark bits only.
+ *
+ * The overflow marks (below) are set per key and per home from the finished
+ * index: from each home of a stored key, every line before the first one that
+ * holds the key carries the key's mark (lines_mark_kernel walks the index,
+ * since a record does not say which home it was inserted from).
  */
 #ifndef KGX_LINE_HOME_H
 #define KGX_LINE_HOME_H
@@ -36,15 +55,18 @@ constexpr uint32_t LINE_HOME_MOD = 0, LINE_HOME_MINIMIZER = 1;
  * key's home bucket is home(key) << hs over num_sigs >> hs homes: 0 the
  * reference slots, 2 the 4-bucket lines of the index), bits 8-15 the
  * LINE_HOME_* mode of the image's index (0 where hs is 0), bit 16 set when
- * the index carries overflow marks (line_mark, below). */
-constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8, HOME_MODE_MASK = 0xFFu, HOME_MARKS_BIT = 1u << 16;
-KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode, bool marks = false)
+ * the index carries overflow marks (line_mark, below), bit 17 set when it
+ * holds twin records (above). */
+constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8, HOME_MODE_MASK = 0xFFu, HOME_MARKS_BIT = 1u << 16,
+                   HOME_TWINS_BIT = 1u << 17;
+KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode, bool marks = false, bool twins = false)
 {
-    return shift | mode << HOME_MODE_SHIFT | (marks ? HOME_MARKS_BIT : 0u);
+    return shift | mode << HOME_MODE_SHIFT | (marks ? HOME_MARKS_BIT : 0u) | (twins ? HOME_TWINS_BIT : 0u);
 }
 KGX_HD uint32_t home_shift_of(uint32_t home) { return home & HOME_SHIFT_MASK; }
 KGX_HD uint32_t home_mode_of(uint32_t home) { return home >> HOME_MODE_SHIFT & HOME_MODE_MASK; }
 KGX_HD bool home_marks_of(uint32_t home) { return (home & HOME_MARKS_BIT) != 0; }
+KGX_HD bool home_twins_of(uint32_t home) { return (home & HOME_TWINS_BIT) != 0; }
 
 /* x % n for x < 2^35, n >= 1, m = floor((2^64-1)/n): the quotient estimate
  * is exact or one short, so one conditional subtraction finishes it */
@@ -85,15 +107,42 @@ KGX_HD void seven_mers(const uint32_t *c, uint32_t &a, uint32_t &b)
     b = (ka - c[0] * 8000u) * 160000u + kb;
 }
 
-/* the minimizer home of the key whose 7-mers are a and b */
+/* the home of the 7-mer m, whose hash mix32(m) is hm */
+KGX_HD uint64_t seven_mer_home(uint32_t m, uint32_t hm, uint64_t n_lines, uint64_t magic)
+{
+    /* 35 bits, the most mod_by takes: a second hash of the 7-mer (hm itself
+     * leans low where it is a minimum) over three low bits of the first */
+    const uint64_t x = (uint64_t)mix32(m ^ 0x85EBCA6Bu) << 3 | (hm & 7u);
+    return mod_by(x, n_lines, magic);
+}
+KGX_HD uint64_t seven_mer_home(uint32_t m, uint64_t n_lines, uint64_t magic)
+{
+    return seven_mer_home(m, mix32(m), n_lines, magic);
+}
+
+/* the minimizer home of the key whose 7-mers are a and b: the home of the one
+ * that hashes lower (a on a tie) */
 KGX_HD uint64_t minimizer_home(uint32_t a, uint32_t b, uint64_t n_lines, uint64_t magic)
 {
     const uint32_t ha = mix32(a), hb = mix32(b);
-    const uint32_t m = ha <= hb ? a : b, hm = ha <= hb ? ha : hb;
-    /* 35 bits, the most mod_by takes: a second hash of the minimizer (hm
-     * itself leans low, being a minimum) over three low bits of the first */
-    const uint64_t x = (uint64_t)mix32(m ^ 0x85EBCA6Bu) << 3 | (hm & 7u);
-    return mod_by(x, n_lines, magic);
+    return ha <= hb ? seven_mer_home(a, ha, n_lines, magic) : seven_mer_home(b, hb, n_lines, magic);
+}
+
+/* the twin home: the home of the other 7-mer (equal to the minimizer home
+ * where a == b, and wherever the two 7-mers happen to share a line) */
+KGX_HD uint64_t twin_home(uint32_t a, uint32_t b, uint64_t n_lines, uint64_t magic)
+{
+    const uint32_t ha = mix32(a), hb = mix32(b);
+    return ha <= hb ? seven_mer_home(b, hb, n_lines, magic) : seven_mer_home(a, ha, n_lines, magic);
+}
+
+/* Where the aligned line probe starts over an index with twin records: window
+ * g of a batch (its global window index) at the home of its last seven
+ * residues when g is even, of its first seven when g is odd.  Windows g
+ * (even) and g + 1 of one sequence share that 7-mer, so they share the line. */
+KGX_HD uint64_t pair_home(uint32_t a, uint32_t b, uint64_t g, uint64_t n_lines, uint64_t magic)
+{
+    return seven_mer_home(g & 1u ? a : b, n_lines, magic);
 }
 
 /* the home line of `key` (<= 20^8) among n_lines, magic = mod_magic(n_lines) */

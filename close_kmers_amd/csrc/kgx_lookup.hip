@@ -933,7 +933,7 @@ __device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ pa
     }
 }
 
-template <int J, int G, bool DNA, bool MARKS>
+template <int J, int G, bool DNA, bool MARKS, bool TWINS>
 __global__ __launch_bounds__(256) void probe_line_kernel(
     const uint8_t *__restrict__ residues, uint64_t n_residues, const uint64_t *__restrict__ seq_off,
     const uint64_t *__restrict__ wbase, const uint32_t *__restrict__ tile_seq, uint32_t n_seq,
@@ -975,7 +975,13 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
      * G = 4).  Its homes come from the 7-mers the encode holds and its slices
      * run probe_slice_aligned; without, the kernel is the generic one below
      * and holds none of the aligned body's instructions or registers */
+    /* TWINS: the index holds every key under the homes of both its 7-mers
+     * (kgx_line_home.h), and a window starts at pair_home of its index in the
+     * batch: g0, 64 j and the 16 windows of an instruction are all even, so
+     * windows g (even) and g + 1 are neighbouring quads of one instruction
+     * and, in one sequence, ask for one line */
     static_assert(!MARKS || G == 4, "the index's lines are 4 records");
+    static_assert(!TWINS || MARKS, "twin records come with marks only");
     if constexpr (MARKS) {
         uint32_t a7[J], b7[J];
         if (DNA)
@@ -988,7 +994,10 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
         uint32_t home_line[J];
 #pragma unroll
         for (int j = 0; j < J; j++) {
-            home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(hs)) : 0;
+            if (TWINS)
+                home_line[j] = ok[j] ? (uint32_t)pair_home(a7[j], b7[j], lane, n_lines, magic) : 0; /* g's parity is the lane's */
+            else
+                home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(hs)) : 0;
             lds_hit[wave][64 * j + lane] = 0;
         }
         /* one 64-window slice at a time, as below */
@@ -1101,10 +1110,11 @@ static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *resi
     /* the aligned slice body, with the mark test, only over an aligned index
      * (kgx_line_home.h); every other table runs the generic kernel, which
      * ignores marks and stays exact */
-    auto *kernel = probe_line_kernel<J, G, DNA, false>;
+    auto *kernel = probe_line_kernel<J, G, DNA, false, false>;
     if constexpr (G == 4)
         if (line_index_aligned(num_sigs, hs))
-            kernel = probe_line_kernel<J, G, DNA, true>;
+            kernel = home_twins_of(hs) ? probe_line_kernel<J, G, DNA, true, true>
+                                       : probe_line_kernel<J, G, DNA, true, false>;
     hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues, n_residues, seq_off, wbase,
                        tile_seq, n_seq, static_cast<const uint4 *>(table), num_sigs,
                        mod_magic(num_sigs >> home_shift_of(hs)), hs, hot, cold, hit_mask, nt);
@@ -1300,12 +1310,17 @@ __global__ __launch_bounds__(256) void count_keys_kernel(const packed_bucket *__
  * from the start of the key's home line (line_home, kgx_line_home.h), 4
  * buckets a line, by a 64-bit CAS on the record's first word.  A probe of the
  * line table from that home finds exactly the records the reference finds, so
- * results are unchanged while nearly every chain ends in its first 64-B line. */
+ * results are unchanged while nearly every chain ends in its first 64-B line.
+ * `twins` (the minimizer home only, kgx_line_home.h): the record is inserted
+ * again by the same walk from its key's twin home, unless that is the same
+ * line; *n_twins counts those second records. */
 __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *__restrict__ src, uint64_t num_sigs,
                                                           uint64_t src_magic, packed_bucket *lines, uint64_t n_lines,
-                                                          uint64_t line_magic, uint32_t home_mode, uint32_t *overflow)
+                                                          uint64_t line_magic, uint32_t home_mode, bool twins,
+                                                          uint32_t *overflow, unsigned long long *n_twins)
 {
     const uint64_t NB = 4 * n_lines;
+    uint64_t made = 0;
     for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < num_sigs;
          b += (uint64_t)gridDim.x * blockDim.x) {
         const packed_bucket e = src[b];
@@ -1322,19 +1337,34 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
         }
         if (!first)
             continue;
-        uint64_t x = line_home(key, n_lines, line_magic, home_mode) * 4;
-        bool placed = false;
-        for (uint64_t n = 0; n < NB && !placed; n++) {
-            const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&lines[x].lo),
-                                                      (unsigned long long)EMPTY_KEY, (unsigned long long)e.lo);
-            if (prev == (unsigned long long)EMPTY_KEY) {
-                lines[x].hi = e.hi;
-                placed = true;
-            }
-            x = x + 1 == NB ? 0 : x + 1;
+        const uint64_t home = line_home(key, n_lines, line_magic, home_mode);
+        uint64_t other = home;
+        if (twins) {
+            const uint32_t a7 = (uint32_t)(key / 20u), b7 = (uint32_t)(key % 1280000000ull);
+            other = twin_home(a7, b7, n_lines, line_magic);
         }
-        if (!placed)
-            atomicOr(overflow, 1u);
+        for (int copy = 0; copy < (other != home ? 2 : 1); copy++) {
+            uint64_t x = (copy ? other : home) * 4;
+            bool placed = false;
+            for (uint64_t n = 0; n < NB && !placed; n++) {
+                const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&lines[x].lo),
+                                                          (unsigned long long)EMPTY_KEY, (unsigned long long)e.lo);
+                if (prev == (unsigned long long)EMPTY_KEY) {
+                    lines[x].hi = e.hi;
+                    placed = true;
+                }
+                x = x + 1 == NB ? 0 : x + 1;
+            }
+            if (!placed)
+                atomicOr(overflow, 1u);
+            made += copy && placed;
+        }
+    }
+    if (twins) {
+        for (int o = 32; o > 0; o >>= 1)
+            made += __shfl_xor(made, o);
+        if (lane_id() == 0 && made)
+            atomicAdd(n_twins, (unsigned long long)made);
     }
 }
 
@@ -1344,10 +1374,21 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
  * kernel of its own, after the inserts: the inserter's plain store of `hi`
  * would race with another key's OR.  SCRATCH: the same marks into a separate
  * array instead, 16 bits per line, two lines per word (kgx_image_line_stats
- * compares the two). */
+ * compares the two).
+ *
+ * `twins`: a key has two homes and a record does not say which one it was
+ * inserted from, so each record walks from both homes of its key and marks
+ * every line before the first one that holds the key (its own line at the
+ * latest: only full lines are passed, and no record ever leaves).  Both copies
+ * of a key do the same two walks; the ORs are idempotent.  The counts are
+ * kept in halves so that they stay per key: a key with one home line adds 2
+ * to stats[0] and 2 to stats[1] if it lies past that line; each of the two
+ * records of a key with two home lines adds 1 to stats[0] and 1 to stats[1]
+ * for each home whose line does not hold the key.  kgx_image_line_stats
+ * halves both sums.  Without twins both are counted whole, as they were. */
 template <bool SCRATCH>
 __global__ __launch_bounds__(256) void lines_mark_kernel(packed_bucket *lines, uint64_t n_lines, uint64_t line_magic,
-                                                         uint32_t home_mode, uint32_t *scratch,
+                                                         uint32_t home_mode, bool twins, uint32_t *scratch,
                                                          unsigned long long *stats)
 {
     const uint64_t NB = 4 * n_lines;
@@ -1356,19 +1397,37 @@ __global__ __launch_bounds__(256) void lines_mark_kernel(packed_bucket *lines, u
         const uint64_t key = lines[b].lo & PACK_KEY_MASK;
         if (key > MAX_ENCODED)
             continue;
-        stored++;
         const uint64_t own = b / 4;
-        uint64_t l = line_home(key, n_lines, line_magic, home_mode);
-        if (l == own)
-            continue;
-        past++;
+        const uint64_t home = line_home(key, n_lines, line_magic, home_mode);
+        uint64_t other = home;
+        if (twins) {
+            const uint32_t a7 = (uint32_t)(key / 20u), b7 = (uint32_t)(key % 1280000000ull);
+            other = twin_home(a7, b7, n_lines, line_magic);
+        }
+        const uint32_t n_homes = other != home ? 2 : 1;
+        const uint32_t unit = twins && n_homes == 1 ? 2 : 1;
+        stored += unit;
         const uint32_t g = line_mark(key);
-        for (; l != own; l = l + 1 == n_lines ? 0 : l + 1) {
-            if (SCRATCH)
-                atomicOr(scratch + (l >> 1), 1u << (g + 16u * (uint32_t)(l & 1)));
-            else
-                atomicOr(reinterpret_cast<unsigned long long *>(&lines[4 * l + mark_record(g)].hi),
-                         1ull << (32 + mark_bit_w(g)));
+        for (uint32_t h = 0; h < n_homes; h++) {
+            uint64_t l = h ? other : home;
+            bool passed = false;
+            while (l != own) {
+                if (twins) { /* the other copy may lie before this one on the chain */
+                    bool holds = false;
+                    for (uint32_t r = 0; r < 4; r++)
+                        holds |= (lines[4 * l + r].lo & PACK_KEY_MASK) == key;
+                    if (holds)
+                        break;
+                }
+                passed = true;
+                if (SCRATCH)
+                    atomicOr(scratch + (l >> 1), 1u << (g + 16u * (uint32_t)(l & 1)));
+                else
+                    atomicOr(reinterpret_cast<unsigned long long *>(&lines[4 * l + mark_record(g)].hi),
+                             1ull << (32 + mark_bit_w(g)));
+                l = l + 1 == n_lines ? 0 : l + 1;
+            }
+            past += passed ? unit : 0;
         }
     }
     if (SCRATCH) {
@@ -1430,22 +1489,23 @@ hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long l
 }
 
 hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t home_mode, bool marks, uint32_t *overflow, hipStream_t stream)
+                              uint32_t home_mode, bool marks, bool twins, uint32_t *overflow,
+                              unsigned long long *n_twins, hipStream_t stream)
 {
     hipLaunchKernelGGL(fill_empty_kernel, dim3(8192), dim3(256), 0, stream, lines, 4 * n_lines);
     hipLaunchKernelGGL(lines_build_kernel, dim3(8192), dim3(256), 0, stream, src, num_sigs, mod_magic(num_sigs), lines,
-                       n_lines, mod_magic(n_lines), home_mode, overflow);
+                       n_lines, mod_magic(n_lines), home_mode, twins, overflow, n_twins);
     if (marks)
         hipLaunchKernelGGL(lines_mark_kernel<false>, dim3(8192), dim3(256), 0, stream, lines, n_lines,
-                           mod_magic(n_lines), home_mode, nullptr, nullptr);
+                           mod_magic(n_lines), home_mode, twins, nullptr, nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, uint32_t *scratch,
-                              unsigned long long *stats, hipStream_t stream)
+hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, bool twins,
+                              uint32_t *scratch, unsigned long long *stats, hipStream_t stream)
 {
     hipLaunchKernelGGL(lines_mark_kernel<true>, dim3(8192), dim3(256), 0, stream, const_cast<packed_bucket *>(lines),
-                       n_lines, mod_magic(n_lines), home_mode, scratch, stats);
+                       n_lines, mod_magic(n_lines), home_mode, twins, scratch, stats);
     hipLaunchKernelGGL(lines_stats_kernel, dim3(8192), dim3(256), 0, stream, lines, n_lines, scratch, stats);
     return hipGetLastError();
 }

@@ -366,6 +366,8 @@ struct kgx_image {
     uint64_t n_lines = 0;
     uint32_t lines_home = kgx::LINE_HOME_MOD; /* the home mode it was built with */
     bool lines_marks = false; /* it carries overflow marks (KGX_LINE_MARKS, kgx_line_home.h) */
+    bool lines_have_twins = false; /* it was built with twin records (KGX_LINE_TWINS, kgx_line_home.h) */
+    uint64_t lines_twins = 0; /* how many: the keys with two home lines */
     uint32_t lines_load = 0; /* keys per 64 lines it was built for */
     uint64_t *d_filter = nullptr;           /* presence filter (kgx_image_set_filter) */
     uint32_t filter_log2_words = 0;
@@ -399,7 +401,7 @@ struct kgx_image {
     /* what the probes read: the line index when there is one */
     const void *probe_table() const { return d_lines ? static_cast<const void *>(d_lines) : resident(); }
     uint64_t probe_buckets() const { return d_lines ? 4 * n_lines : num_sigs; }
-    uint32_t home_shift() const { return d_lines ? kgx::home_word(2u, lines_home, lines_marks) : 0u; }
+    uint32_t home_shift() const { return d_lines ? kgx::home_word(2u, lines_home, lines_marks, lines_have_twins) : 0u; }
 };
 
 struct kgx_ctx {

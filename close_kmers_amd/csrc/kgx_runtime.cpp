@@ -899,6 +899,16 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
         else if (strcmp(v, "1") && *v)
             return fail(KGX_EINVAL, std::string("KGX_LINE_MARKS: 0 (none) or 1 (marks), not \"") + v + "\"");
     }
+    /* twin records, which let two neighbouring windows always share a line
+     * (kgx_line_home.h): KGX_LINE_TWINS 1 (the default) builds them where the
+     * rule of kgx.h allows, 0 builds none; read at each call like the two above */
+    bool twins = home_mode == kgx::LINE_HOME_MINIMIZER && marks && keys_per_64_lines <= KGX_LINE_TWINS_MAX_LOAD;
+    if (const char *v = getenv("KGX_LINE_TWINS")) {
+        if (!strcmp(v, "0"))
+            twins = false;
+        else if (strcmp(v, "1") && *v)
+            return fail(KGX_EINVAL, std::string("KGX_LINE_TWINS: 0 (none) or 1 (twins), not \"") + v + "\"");
+    }
     /* the service's workgroups hold the probe table's address */
     const auto hold = svc_shutdown_hold(img);
     HIP_TRY(hipSetDevice(img->device));
@@ -907,15 +917,16 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
         (void)hipFree(img->d_lines);
     img->d_lines = nullptr;
     img->n_lines = 0;
+    img->lines_twins = 0;
     if (!keys_per_64_lines)
         return KGX_OK;
     if (img->layout != KGX_LAYOUT_PACKED16)
         return fail(KGX_EINVAL, "a line index needs a PACKED16 image");
-    unsigned long long *d_count = nullptr;
+    unsigned long long *d_count = nullptr; /* stored keys, twin records, the overflow flag */
     uint32_t *d_over = nullptr;
-    HIP_TRY(hipMalloc(&d_count, 16));
-    d_over = reinterpret_cast<uint32_t *>(d_count + 1);
-    hipError_t e = hipMemset(d_count, 0, 16);
+    HIP_TRY(hipMalloc(&d_count, 24));
+    d_over = reinterpret_cast<uint32_t *>(d_count + 2);
+    hipError_t e = hipMemset(d_count, 0, 24);
     if (e == hipSuccess)
         e = launch_count_keys(img->d_packed, img->num_sigs, d_count, nullptr);
     unsigned long long n_keys = 0;
@@ -933,10 +944,14 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
         return fail(KGX_ENOMEM, "no room for the line index (" + std::to_string(4 * n_lines * 16) + " B)");
     }
     uint32_t over = 0;
+    unsigned long long n_twins = 0;
     if (e == hipSuccess)
-        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, marks, d_over, nullptr);
+        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, marks, twins, d_over,
+                               d_count + 1, nullptr);
     if (e == hipSuccess)
         e = hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(&n_twins, d_count + 1, 8, hipMemcpyDeviceToHost);
     (void)hipFree(d_count);
     if (e != hipSuccess || over) {
         if (lines)
@@ -948,12 +963,15 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     img->n_lines = n_lines;
     img->lines_home = home_mode;
     img->lines_marks = marks;
+    img->lines_twins = n_twins;
+    img->lines_have_twins = twins;
     img->lines_load = keys_per_64_lines;
     return KGX_OK;
 }
 
 uint64_t kgx_image_line_count(const kgx_image *img) { return img ? img->n_lines : 0; }
 uint32_t kgx_image_line_home(const kgx_image *img) { return img && img->d_lines ? img->lines_home : 0; }
+uint64_t kgx_image_line_twins(const kgx_image *img) { return img && img->d_lines ? img->lines_twins : 0; }
 
 int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
 {
@@ -972,7 +990,8 @@ int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
     unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_scratch);
     hipError_t e = hipMemset(d_scratch, 0, words * 4 + 64);
     if (e == hipSuccess)
-        e = launch_lines_stats(img->d_lines, img->n_lines, img->lines_home, d_scratch + 16, d_stats, nullptr);
+        e = launch_lines_stats(img->d_lines, img->n_lines, img->lines_home, img->lines_have_twins, d_scratch + 16,
+                               d_stats, nullptr);
     unsigned long long h[8] = {};
     if (e == hipSuccess)
         e = hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost);
@@ -981,6 +1000,10 @@ int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
         return fail(KGX_EDEVICE, std::string("line statistics: ") + hipGetErrorString(e));
     for (int i = 0; i < 8; i++)
         out[i] = h[i];
+    if (img->lines_have_twins) { /* counted in halves, per key (lines_mark_kernel) */
+        out[0] /= 2;
+        out[1] /= 2;
+    }
     return KGX_OK;
 }
 

@@ -299,15 +299,42 @@ int kgx_image_set_layout(kgx_image *img, int layout);
  * off: 1 builds marks (the default), 0 builds none; any other value is
  * KGX_EINVAL and the index the image had is kept.  Which bits are set depends
  * on the build's insertion order and differs from build to build; results do
- * not. */
+ * not.
+ * Twin records.  Under the minimizer home with marks, and at loads up to
+ * KGX_LINE_TWINS_MAX_LOAD, every key whose two 7-mers are homed on different
+ * lines is stored twice, once from each home, in the same n_lines (at load 36
+ * the records fill 28% of the buckets instead of 14%).  The batch line probe
+ * then starts a window with an even index in its batch at the home of its
+ * last seven residues and an odd one at the home of its first seven: the two
+ * windows of such a pair in one sequence always ask for the same line, half a
+ * line per window at best where the minimizer alone gives two thirds.  Every
+ * other prober keeps starting at the minimizer home and finds what it found.
+ * The environment variable KGX_LINE_TWINS, read at each call like the two
+ * above: 1 (the default) builds twins where this rule allows, 0 builds none
+ * (the index of the paragraphs above, unchanged); any other value is
+ * KGX_EINVAL and the index the image had is kept.  The cut is where the
+ * doubled records fill half of the buckets.  tools/line_home_model.py
+ * (--load), requests per window of a benchmark-shaped batch with twins
+ * against without: load 36 0.554 / 0.697, 48 0.585 / 0.700, 64 0.663 / 0.706,
+ * 80 0.847 / 0.714, 96 1.448 / 0.726 (full lines with twins: 12%, 19%, 31%,
+ * 44%, 61%).  Twins pay up to load 64 and cost past it; at load 255 the
+ * doubled records would not fit at all.  The price at every load is paid by
+ * the probers that start at the minimizer home: their chains cross the fuller
+ * lines (the call service's p50 is a quarter longer at load 36, DESIGN.md
+ * section 5); KGX_LINE_TWINS=0 is for images that serve those. */
+#define KGX_LINE_TWINS_MAX_LOAD 64u
 int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines);
 /* lines of the image's line index (0: none) */
 uint64_t kgx_image_line_count(const kgx_image *img);
 /* the KGX_LINE_HOME mode the image's line index was built with (0: mod or
  * no index, 1: minimizer) */
 uint32_t kgx_image_line_home(const kgx_image *img);
-/* A device pass over the line index: out[0] stored records, [1] records past
- * their home line, [2] full lines, [3] lines with any overflow mark, [4] mark
+/* twin records in the image's line index: the keys with two distinct home
+ * lines (0: built without twins, or no index) */
+uint64_t kgx_image_line_twins(const kgx_image *img);
+/* A device pass over the line index: out[0] stored keys (a key with a twin
+ * record counts once), [1] records past their home line (with twins: pairs of
+ * a key and one of its home lines where that line does not hold the key), [2] full lines, [3] lines with any overflow mark, [4] mark
  * bits set, [5] missing marks (a stored key lies past a line whose bit for it
  * is clear; 0 for an index with marks, else probes would miss stored keys),
  * [6] unjustified marks (a set bit that no stored key past that line calls
@@ -315,7 +342,8 @@ uint32_t kgx_image_line_home(const kgx_image *img);
  * 0.  An index built with KGX_LINE_MARKS=0 has [3] = [4] = [6] = 0 and [5]
  * the marks it would carry.  The marks called for are recomputed by the walk
  * that set them (from each displaced record's home line to the line before
- * its own), so [5] = [6] = 0 says that the index holds exactly that walk's
+ * its own; with twins, from each home of a key to the line before the first
+ * that holds it), so [5] = [6] = 0 says that the index holds exactly that walk's
  * marks and no stray bit; that the walk itself is the right one is what the
  * comparisons with the reference's results check.  KGX_EINVAL without a line
  * index; needs 2 B per line of device memory while it runs. */

@@ -10,6 +10,12 @@ index at the benchmark's ratios and counts those lines under
     minimizer  home = hash of whichever of the key's two 7-mers hashes lower
                (csrc/kgx_line_home.h), so neighbouring windows of a sequence
                share their home line one time in three
+    twins      the minimizer index with every key stored a second time from
+               the home of its other 7-mer (twin records, KGX_LINE_TWINS); a
+               window with an even index in the batch is looked up from the
+               home of its last seven residues and the odd window after it
+               from the home of its first seven, the same 7-mer, so the two
+               always share their line and one instruction serves both
 
 for stored keys, for absent keys, and for a query batch shaped like the
 benchmark's (half the sequences planted copies of source proteins with 10%
@@ -32,7 +38,7 @@ lines: 0.78 keys and 1.39 lines per 7-mer.  The model keeps those two ratios
 over a smaller alphabet (default 10 letters: 1e7 7-mers) so that the table
 fits in memory; sharing and lumpiness depend on the ratios, not on the size.
 
-    python tools/line_home_model.py [--alphabet 10] [--seed 1] [--json]
+    python tools/line_home_model.py [--alphabet 10] [--seed 1] [--load 36] [--json]
 """
 import argparse
 import json
@@ -64,6 +70,17 @@ def homes(keys, n_lines, mode, alpha):
     hm = np.minimum(ha, hb)
     x = (mix32(m ^ np.uint64(0x85EBCA6B)) << np.uint64(3)) | (hm & np.uint64(7))
     return (x % np.uint64(n_lines)).astype(np.int64)
+
+
+def seven_mer_homes(keys, n_lines, alpha):
+    """the homes of a key's two 7-mers (seven_mer_home) and whether the first
+    one is the minimizer"""
+    keys = keys.astype(np.uint64)
+    a, b = keys // np.uint64(alpha), keys % np.uint64(alpha ** 7)
+    ha, hb = mix32(a), mix32(b)
+    xa = (mix32(a ^ np.uint64(0x85EBCA6B)) << np.uint64(3)) | (ha & np.uint64(7))
+    xb = (mix32(b ^ np.uint64(0x85EBCA6B)) << np.uint64(3)) | (hb & np.uint64(7))
+    return (xa % np.uint64(n_lines)).astype(np.int64), (xb % np.uint64(n_lines)).astype(np.int64), ha <= hb
 
 
 def line_mark(keys):
@@ -118,9 +135,13 @@ def set_marks(keys, home, at, n_lines, bits):
     """the marks of a built index: every key placed past its home line sets
     bit line_mark(key) (bit 0 when bits == 1) on each line from its home to
     the one before its own"""
+    return set_marks_walk(keys, home, (at // 4 - home) % n_lines, n_lines, bits)
+
+
+def set_marks_walk(keys, home, walk, n_lines, bits):
+    """the same for keys that pass `walk` lines from `home`"""
     marks = np.zeros(n_lines, np.uint32)
     g = line_mark(keys) if bits == 16 else np.zeros(len(keys), np.int64)
-    walk = (at // 4 - home) % n_lines
     todo = np.nonzero(walk > 0)[0]
     d = 0
     while len(todo):
@@ -156,11 +177,84 @@ def tile_requests(qh, q_lines, n_lines, tile=128):
     return len(np.unique(touched)) / len(h)
 
 
-def model(alpha, seed):
+def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
+    """the minimizer index with twin records, probed by the even/odd choice;
+    the columns of the other two homes"""
+    n = len(keys)
+    hA, hB, amin = seven_mer_homes(keys, n_lines, alpha)
+    two = hA != hB
+    h1, h2 = np.where(amin, hA, hB), np.where(amin, hB, hA)
+    at, occ = build(np.concatenate([h1, h2[two]]), n_lines)  # every record goes to its walk's first empty bucket
+    line1 = at[:n] // 4
+    line2 = line1.copy()
+    line2[two] = at[n:] // 4
+    # lines passed from a home before the first line that holds the key
+    dA = np.minimum((line1 - hA) % n_lines, (line2 - hA) % n_lines)
+    dB = np.minimum((line1 - hB) % n_lines, (line2 - hB) % n_lines)
+    per_home = np.concatenate([np.where(amin, dA, dB), np.where(amin, dB, dA)[two]]) + 1
+    run = full_run(occ, n_lines)
+    full = run > 0
+    # queries: window g of the batch (sequences laid end to end) starts at
+    # the home of its first 7-mer when g is odd, of its last when g is even
+    odd = (np.arange(qk.size).reshape(qk.shape) & 1).astype(bool)
+    qA, qB, _ = seven_mer_homes(qk.ravel(), n_lines, alpha)
+    qh = np.where(odd, qA.reshape(qk.shape), qB.reshape(qk.shape))
+    pos = np.minimum(np.searchsorted(skeys, qk.ravel()), len(skeys) - 1)
+    present = (skeys[pos] == qk.ravel()).reshape(qk.shape)
+    idx = order[pos].reshape(qk.shape)
+    ql_present = np.where(odd, dA[idx], dB[idx]) + 1
+    aA, aB, _ = seven_mer_homes(absent, n_lines, alpha)
+    ah = np.where(np.arange(len(absent)) & 1, aA, aB)
+    same = qh[:, 1:] == qh[:, :-1]
+    pair = same & ~odd[:, :-1]  # the even window and the one after it: neighbouring quads of one instruction
+    keys2, home2, walk2 = np.concatenate([keys, keys]), np.concatenate([hA, hB]), np.concatenate([dA, dB])
+    variants = {}
+    for bits in (0, 1, 16):
+        if bits:
+            mk = set_marks_walk(keys2, home2, walk2, n_lines, bits)
+            la = marked_chain(absent, ah, full, mk, n_lines, bits)
+            ql = np.where(present, ql_present,
+                          marked_chain(qk.ravel(), qh.ravel(), full, mk, n_lines, bits).reshape(qk.shape))
+        else:
+            mk, la, ql = np.zeros(n_lines, np.uint32), run[ah] + 1, np.where(present, ql_present, run[qh] + 1)
+        sv = np.where(pair, np.minimum(ql[:, 1:], ql[:, :-1]), 0)
+        variants[str(bits)] = {
+            "query_lines_per_window": float(ql.mean()),
+            "query_windows_past_first_line": float((ql > 1).mean()),
+            "lines_per_absent_key": float(la.mean()),
+            "query_lines_per_absent_window": float(ql[~present].mean()),
+            "query_lines_per_present_window": float(ql[present].mean()),
+            "query_requests_per_window": float((ql.sum() - sv.sum()) / ql.size),
+            "query_requests_per_window_tile_merge": float(tile_requests(qh, ql, n_lines)),
+            "lines_marked": float((mk != 0).mean()),
+            "mark_bits_per_marked_line": float(np.array([bin(int(v)).count("1") for v in mk[mk != 0][:100000]]).mean())
+            if (mk != 0).any() else 0.0,
+        }
+    q0 = variants["0"]
+    return {
+        "query_windows_absent": float((~present).mean()),
+        "marks": variants,
+        "twin_records_per_key": float(two.mean()),
+        "buckets_filled": float(occ.mean()),
+        "lines_per_present_key": float(per_home.mean()),
+        "present_keys_past_first_line": float((per_home > 1).mean()),
+        "longest_chain_lines": int(per_home.max()),
+        "full_lines": float(full.mean()),
+        "lines_per_absent_key": float((run[ah] + 1).mean()),
+        "query_lines_per_window": q0["query_lines_per_window"],
+        "query_windows_past_first_line": q0["query_windows_past_first_line"],
+        "neighbours_sharing_home": float(same.mean()),
+        "neighbours_sharing_home_planted": float(same[:n_q // 2].mean()),
+        "neighbours_sharing_home_uniform": float(same[n_q // 2:].mean()),
+        "query_requests_per_window": q0["query_requests_per_window"],
+    }
+
+
+def model(alpha, seed, load=36):
     rng = np.random.default_rng(seed)
     n7 = alpha ** 7
     n_keys = int(0.78125 * n7)    # 1.0e9 / 1.28e9
-    n_lines = int(1.3889 * n7) | 1  # 1.778e9 / 1.28e9 (36 keys per 64 lines), odd
+    n_lines = int(n_keys * 64 / load) | 1  # 36 keys per 64 lines: 1.778e9 / 1.28e9 = 1.39 per 7-mer; odd
     n_src = (n_keys // 4) // 292
     src = rng.integers(0, alpha, (n_src, 300), dtype=np.int8)
     planted = windows(src, alpha).ravel()
@@ -181,6 +275,7 @@ def model(alpha, seed):
 
     out = {"alphabet": alpha, "seven_mers": n7, "keys": len(keys), "lines": n_lines,
            "keys_per_7mer": len(keys) / n7, "lines_per_7mer": n_lines / n7, "homes": {}}
+    out["homes"]["twins"] = None  # printed last
     for mode in ("mod", "minimizer"):
         h = homes(keys, n_lines, mode, alpha)
         at, occ = build(h, n_lines)
@@ -242,6 +337,8 @@ def model(alpha, seed):
             "neighbours_sharing_home_uniform": float(same[n_q // 2:].mean()),
             "query_requests_per_window": float(requests),
         }
+    del out["homes"]["twins"]
+    out["homes"]["twins"] = twins_model(keys, skeys, np.argsort(keys), absent, qk, n_q, n_lines, alpha)
     return out
 
 
@@ -249,9 +346,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--alphabet", type=int, default=10)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--load", type=int, default=36, help="keys per 64 lines (kgx_image_set_line_index)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
-    r = model(a.alphabet, a.seed)
+    r = model(a.alphabet, a.seed, a.load)
     if a.json:
         print(json.dumps(r))
         return
