@@ -1,6 +1,6 @@
 """Compile the gfx950 engine in-tree.
 
-    libkgx.so   kernels (csrc/kgx_kernels.hip) + C ABI runtime + KmerGuts facade
+    libkgx.so   kernels (csrc/*.hip, LIB_SOURCES below) + C ABI runtime + KmerGuts facade
     kgx_query   request-handler surface driver linked against libkgx.so
     kgx_server  the kser HTTP request server (krequest2.cc routes) over libkgx.so
 
@@ -30,7 +30,8 @@ WAVE_SORT_CHECK = os.path.join(ROOT, "tests", "native", "wave_sort_check")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["kgx_lookup.hip", "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.hip", "kgx_fq.hip", "kgx_sig.hip",
+LIB_SOURCES = ["kgx_plan.hip", "kgx_probe.hip", "kgx_line_index.hip", "kgx_score.hip", "kgx_gather.hip",
+               "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.hip", "kgx_fq.hip", "kgx_sig.hip",
                "kgx_runtime.cpp",
                "kgx_host_batch.cpp", "kgx_pool.cpp", "kgx_svc.cpp", "kguts_hip.cpp", "kgx_handlers.cpp"]
 HEADERS = ["kgx_internal.h", "kgx_device.h", "kgx_line_home.h", "kguts_hip.h", "kgx_rt.h", "kgx_lstd.h", "kgx_handlers.h",

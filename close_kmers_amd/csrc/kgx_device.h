@@ -140,6 +140,28 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+/* inclusive scan over a 256-thread workgroup; `total` = sum of all */
+__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *lds4, uint64_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint64_t x = __shfl_up(v, off);
+        if (lane >= off)
+            v += x;
+    }
+    if (lane == 63)
+        lds4[wave] = v;
+    __syncthreads();
+    uint64_t pre = 0;
+    total = 0;
+    for (uint32_t i = 0; i < 4; i++) {
+        if (i < wave)
+            pre += lds4[i];
+        total += lds4[i];
+    }
+    return v + pre;
+}
+
 /* ---- hit records (kgx_internal.h: HIT_PLANES / HIT_PACKED16) ---- */
 
 /* the fields of one hit record (hot = plane 0 / the packed record,

@@ -43,7 +43,7 @@ struct FusedArgs {
     uint32_t want;
     const uint4 *table; /* PACKED16 records in HBM */
     uint64_t num_sigs, magic; /* buckets; magic of num_sigs >> the home shift */
-    uint32_t hs;              /* home shift and mode: home_bucket (kgx_line_home.h) */
+    uint32_t home;            /* the home word: home_bucket (kgx_line_home.h) */
     kgx_params prm;
     kgx_hit *hits;    /* mapped: sequence s's hits from hits[wbase[s]] */
     kgx_call *calls;  /* mapped: sequence s's calls from calls[wbase[s]] */
@@ -171,7 +171,7 @@ __device__ __forceinline__ void fused_small_body(const FusedArgs &a, const IN &k
                 const uint32_t kb = ((c[4] * 20u + c[5]) * 20u + c[6]) * 20u + c[7];
                 k = (uint64_t)ka * 160000u + kb;
                 pd = cmax < 20u;
-                sl = pd ? home_bucket(k, a.num_sigs, a.magic, a.hs) : 0;
+                sl = pd ? home_bucket(k, a.num_sigs, a.magic, a.home) : 0;
             };
 #pragma unroll
             for (uint32_t j = 0; j < RB; j++) {
@@ -790,14 +790,14 @@ __device__ __forceinline__ void fused_small_body(const FusedArgs &a, const IN &k
 }
 
 hipError_t launch_fused_small(const uint8_t *res, const uint64_t *off, const uint64_t *wbase, uint32_t n,
-                              uint32_t want, const void *packed_table, uint64_t num_sigs, kgx_params prm,
+                              uint32_t want, const ProbeTable &t, kgx_params prm,
                               kgx_hit *hits, kgx_call *calls, uint32_t *counts, uint32_t *done, uint32_t token,
                               uint32_t max_windows, uint64_t *dbg, const uint64_t *h_off, const uint64_t *h_wbase,
-                              const uint8_t *h_res, uint32_t inline_res, hipStream_t stream, uint32_t hs)
+                              const uint8_t *h_res, uint32_t inline_res, hipStream_t stream)
 {
     if (n == 0)
         return hipSuccess;
-    if (n > FUSED_MAX_SEQ || num_sigs == 0 || !packed_table)
+    if (n > FUSED_MAX_SEQ || t.num_sigs == 0 || !t.buckets)
         return hipErrorInvalidValue;
     FusedArgs a;
     a.res = res;
@@ -805,10 +805,10 @@ hipError_t launch_fused_small(const uint8_t *res, const uint64_t *off, const uin
     a.wbase = wbase;
     a.n = n;
     a.want = want;
-    a.table = static_cast<const uint4 *>(packed_table);
-    a.num_sigs = num_sigs;
-    a.magic = mod_magic(num_sigs >> home_shift_of(hs));
-    a.hs = hs;
+    a.table = static_cast<const uint4 *>(t.buckets);
+    a.num_sigs = t.num_sigs;
+    a.magic = t.magic();
+    a.home = t.home;
     a.prm = prm;
     a.hits = hits;
     a.calls = calls;
@@ -875,7 +875,7 @@ __global__ __launch_bounds__(256) void svc_kernel(const SvcSlotHdr *hdr, SvcSlot
                                                   const uint8_t *res_base, kgx_hit *hits, kgx_call *calls,
                                                   kgx_otu *otus,
                                                   const uint4 *table, uint64_t num_sigs, uint64_t magic,
-                                                  uint32_t hs, uint64_t life_ticks, uint32_t poll_chunks)
+                                                  uint32_t home, uint64_t life_ticks, uint32_t poll_chunks)
 {
     __shared__ uint32_t cmd[18]; /* the request's header line; [16] = go, [17] = chunks still stale */
     __shared__ uint32_t scodes[SVC_RES_CHUNKS * 3]; /* the request's residue codes, 12 per chunk */
@@ -980,7 +980,7 @@ __global__ __launch_bounds__(256) void svc_kernel(const SvcSlotHdr *hdr, SvcSlot
         a.table = table;
         a.num_sigs = num_sigs;
         a.magic = magic;
-        a.hs = hs;
+        a.home = home;
         a.prm = h->prm;
         a.hits = hits + (uint64_t)slot * FUSED_MAX_WINDOWS;
         a.calls = calls + (uint64_t)slot * FUSED_MAX_WINDOWS;
@@ -1013,20 +1013,19 @@ __global__ __launch_bounds__(256) void svc_kernel(const SvcSlotHdr *hdr, SvcSlot
 }
 
 hipError_t launch_svc(const SvcSlotHdr *hdr, SvcSlotOut *out, SvcSlotDbg *dbg, const uint8_t *res, kgx_hit *hits,
-                      kgx_call *calls, kgx_otu *otus, uint32_t slots, const void *packed_table, uint64_t num_sigs,
-                      uint64_t life_ticks, int quad_probe, hipStream_t stream, uint32_t hs, uint32_t poll_chunks)
+                      kgx_call *calls, kgx_otu *otus, uint32_t slots, const ProbeTable &t,
+                      uint64_t life_ticks, int quad_probe, hipStream_t stream, uint32_t poll_chunks)
 {
     poll_chunks = std::min(poll_chunks, SVC_POLL_CHUNKS);
-    if (slots == 0 || slots > SVC_MAX_SLOTS || num_sigs == 0 || !packed_table)
+    if (slots == 0 || slots > SVC_MAX_SLOTS || t.num_sigs == 0 || !t.buckets)
         return hipErrorInvalidValue;
-    const uint64_t magic = mod_magic(num_sigs >> home_shift_of(hs));
     if (quad_probe)
         hipLaunchKernelGGL(svc_kernel<true>, dim3(slots), dim3(256), 0, stream, hdr, out, dbg, res, hits, calls, otus,
-                           static_cast<const uint4 *>(packed_table), num_sigs, magic, hs,
+                           static_cast<const uint4 *>(t.buckets), t.num_sigs, t.magic(), t.home,
                            life_ticks, poll_chunks);
     else
         hipLaunchKernelGGL(svc_kernel<false>, dim3(slots), dim3(256), 0, stream, hdr, out, dbg, res, hits, calls,
-                           otus, static_cast<const uint4 *>(packed_table), num_sigs, magic, hs,
+                           otus, static_cast<const uint4 *>(t.buckets), t.num_sigs, t.magic(), t.home,
                            life_ticks, poll_chunks);
     return hipGetLastError();
 }

@@ -1366,8 +1366,7 @@ int process_batch_fused(kgx_ctx *c, const kgx_params &p, const char *residues, c
         HIP_TRY(c->h_fdbg.device_ptr(0, &d_dbg));
     }
     HIP_TRY(launch_fused_small(static_cast<const uint8_t *>(d_res), static_cast<const uint64_t *>(d_off),
-                               static_cast<const uint64_t *>(d_wb), n_seq, want, ctx_probe_table(c),
-                               ctx_probe_buckets(c), p,
+                               static_cast<const uint64_t *>(d_wb), n_seq, want, ctx_probe_table(c), p,
                                static_cast<kgx_hit *>(d_hits), static_cast<kgx_call *>(d_calls),
                                static_cast<uint32_t *>(d_counts), static_cast<uint32_t *>(d_done), token,
                                (uint32_t)longest, static_cast<uint64_t *>(d_dbg), c->h_off_stage.data(),
@@ -1375,7 +1374,7 @@ int process_batch_fused(kgx_ctx *c, const kgx_params &p, const char *residues, c
                                c->opt.fused_inline && n_seq <= FUSED_INLINE_SEQ && off[n_seq] <= FUSED_INLINE_RES
                                    ? (uint32_t)std::max<uint64_t>(off[n_seq], 1)
                                    : 0u,
-                               c->stream, ctx_home_shift(c)));
+                               c->stream));
     /* every sequence's token (stored after its results, behind a
      * system-scope fence); a fault or a lost store still ends the wait */
     const volatile uint32_t *done = c->h_fdone.data();

@@ -1,6 +1,7 @@
 /*
- * kgx_internal.h -- shared definitions between the HIP kernels
- * (kgx_lookup.hip, kgx_synth.hip) and the host runtime (kgx_runtime.cpp).
+ * kgx_internal.h -- shared definitions between the HIP kernels (kgx_plan.hip,
+ * kgx_probe.hip, kgx_line_index.hip, kgx_score.hip, kgx_gather.hip,
+ * kgx_fused.hip, kgx_synth.hip) and the host runtime (kgx_runtime.cpp).
  */
 #ifndef KGX_INTERNAL_H
 #define KGX_INTERNAL_H
@@ -140,6 +141,8 @@ __host__ __device__ inline uint64_t filter_bits(uint64_t h)
 inline uint64_t mod_magic(uint64_t n) { return n ? (~0ULL) / n : 0; }
 
 /* launchers; all asynchronous on `stream` */
+
+/* ---- kgx_plan.hip: window bases and tile owners of a batch ---- */
 size_t plan_workspace_bytes(uint32_t n_seq);
 /* status[0] = 1 when the offsets are not monotone or span more than
  * n_residues bytes (the batch is then planned as empty), else 0 */
@@ -157,19 +160,26 @@ hipError_t launch_plan_one(const uint64_t *seq_off, uint32_t n_seq, uint64_t n_r
 hipError_t launch_plan_fused(const uint64_t *seq_off, uint32_t n_seq, uint64_t n_residues, uint64_t *wbase,
                              uint32_t *tile_seq, uint32_t tile_windows, uint64_t max_tiles, void *look,
                              uint32_t *status, hipStream_t stream);
-/* Probes of PACKED16 records take home_shift, the word of kgx_line_home.h
- * (home_word: shift | home mode << 8 | overflow marks << 16): a key's home bucket is
- * line_home(key, num_sigs >> shift, mode) << shift and num_sigs counts the
- * table's buckets.  0: the reference's slot (key mod num_sigs); shift 2: the
- * line index of kgx_image_set_line_index (4-bucket lines, homes at line
- * starts), with the home mode the index was built with. */
+
+/* ---- kgx_probe.hip: the probes ---- */
+/* Probes of PACKED16 records take the home word of kgx_line_home.h
+ * (home_word: shift | home mode << 8 | overflow marks << 16 | twins << 17): a
+ * key's home bucket is line_home(key, num_sigs >> shift, mode) << shift and
+ * num_sigs counts the table's buckets.  0: the reference's slot (key mod
+ * num_sigs); shift 2: the line index of kgx_image_set_line_index (4-bucket
+ * lines, homes at line starts), with the home mode the index was built with. */
+struct ProbeTable {           /* what a probe reads */
+    const void *buckets;      /* AOS24 or PACKED16 records */
+    uint64_t num_sigs;        /* how many */
+    uint32_t home;            /* the home word of kgx_line_home.h; 0 = the reference's slots */
+    uint64_t magic() const { return mod_magic(num_sigs >> home_shift_of(home)); }
+};
 hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint64_t *seq_off,
                         const uint64_t *wbase, const uint32_t *tile_seq, uint32_t n_seq,
-                        uint64_t max_tiles, const void *table, int layout, uint64_t num_sigs,
+                        uint64_t max_tiles, const ProbeTable &t, int layout,
                         const uint64_t *filter, uint32_t filter_log2_words,
                         uint4 *hot, uint4 *cold, uint64_t *hit_mask, int probe_j, int variant,
-                        uint32_t lds_kb, uint32_t max_blocks, hipStream_t stream, uint32_t home_shift = 0,
-                        uint32_t nt_stores = 0);
+                        uint32_t lds_kb, uint32_t max_blocks, hipStream_t stream, uint32_t nt_stores = 0);
 /* nt_stores 1: the line probe writes its hit records and mask words with
  * non-temporal stores (context option "probe_nt", an A/B knob).
  * max_blocks > 0 caps the line probe's grid (its waves then stride over the
@@ -178,33 +188,21 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
  * 1-4): anchor[s] = (first base of fragment s) << 1 | reverse strand; keys as
  * launch_probe over the translated residues (HIT_PACKED16 records) */
 hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64_t *anchor, const uint64_t *wbase,
-                            const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const void *table,
-                            uint64_t num_sigs, uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks,
-                            hipStream_t stream, uint32_t home_shift = 0);
-/* set the filter bits of every stored key of the resident table */
-hipError_t launch_filter_build(const void *table, int layout, uint64_t num_sigs, uint64_t *filter,
-                               uint32_t log2_words, hipStream_t stream);
-/* *count += the PACKED16 table's stored keys */
-hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned long long *count, hipStream_t stream);
-/* the line index of a PACKED16 table (lines_build_kernel): 4 * n_lines
- * buckets, homes by line_home(home_mode); *overflow |= 1 when some record
- * found no bucket; marks: then the overflow marks of kgx_line_home.h, by
- * lines_mark_kernel; twins (minimizer home with marks only): every key with
- * two home lines is stored under both, *n_twins += those second records */
-hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines, uint64_t n_lines,
-                              uint32_t home_mode, bool marks, bool twins, uint32_t *overflow,
-                              unsigned long long *n_twins, hipStream_t stream);
-/* kgx_image_line_stats: stats[0..7) += stored keys, records past their
- * home line (both twice over an index with twins, see lines_mark_kernel),
- * full lines, lines with a mark, mark bits set, missing and unjustified
- * marks; scratch: (n_lines + 1) / 2 zeroed words */
-hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, bool twins,
-                              uint32_t *scratch, unsigned long long *stats, hipStream_t stream);
+                            const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const ProbeTable &t,
+                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks,
+                            hipStream_t stream);
+
+/* ---- kgx_line_index.hip: the resident layouts and the presence filter ---- */
 /* AoS -> packed; *not_packable |= 1 when some stored bucket does not fit */
 hipError_t launch_pack(const kgx_sig_kmer *table, packed_bucket *packed, uint64_t n,
                        uint32_t *not_packable, hipStream_t stream);
 hipError_t launch_unpack(const packed_bucket *packed, kgx_sig_kmer *out, uint64_t n,
                          hipStream_t stream);
+/* set the filter bits of every stored key of the resident table */
+hipError_t launch_filter_build(const void *table, int layout, uint64_t num_sigs, uint64_t *filter,
+                               uint32_t log2_words, hipStream_t stream);
+
+/* ---- kgx_score.hip: calls, best calls and OTU tallies from the tiled hits ---- */
 /* the run scorer.  variant SCORE_HYBRID (0, the default): the lane machine
  * (one lane per sequence), except sequences of (LONG_SEQ, RUN_CAP] windows,
  * which the wave-parallel scorer takes; SCORE_WAVE (1): the wave scorer for
@@ -218,6 +216,32 @@ hipError_t launch_score(uint32_t n_seq, uint64_t n_residues, const uint64_t *wba
                         kgx_call *calls, void *ranges, uint32_t *hit_count, uint32_t *call_count,
                         kgx_params params, uint32_t want, uint32_t hit_format, int variant, uint32_t wave_tiles,
                         const uint32_t *plan_status, hipStream_t stream);
+/* find_best_call per sequence: calls[start[s] ..+ count[s]), ws same extent */
+hipError_t launch_best_calls(uint32_t n_seq, const kgx_call *calls, const uint64_t *start, const uint32_t *count,
+                             kgx_call *ws, kgx_best_call *out, hipStream_t stream);
+/* per-sequence OTU tallies in otus_by_count order at otus[window_base[s]] */
+hipError_t launch_otus(uint32_t n_seq, const uint64_t *wbase, const uint64_t *hit_mask, uint32_t tile_windows,
+                       const uint4 *hot, const uint4 *cold, int32_t *ws, kgx_otu *otus, uint32_t *otu_count,
+                       uint32_t hit_format, hipStream_t stream);
+
+/* ---- kgx_gather.hip: dense results and their way to the host ---- */
+/* small_collect + gather in one workgroup, for batches of up to
+ * SMALL_GATHER_SEQ sequences (offsets into mapped h0..h2, records into the
+ * mapped outputs; a NULL output is not gathered); last, token is stored to
+ * mapped *done_host (when not NULL) after a system-scope fence, by the last
+ * workgroup to finish (blocks_done: a zeroed device word the kernel leaves
+ * zeroed; NULL = one workgroup) */
+constexpr uint32_t SMALL_GATHER_SEQ = 256;
+constexpr uint32_t SMALL_COLLECT_BEST_SEQ = 8192;
+constexpr uint32_t SMALL_GATHER_BLOCKS = 64; /* workgroups of the small gather (one wave per sequence) */
+hipError_t launch_small_gather(uint32_t n, const uint64_t *wbase, const uint64_t *hit_mask, uint32_t tile_windows,
+                               const uint32_t *hit_count, const uint32_t *call_count, const uint4 *hot,
+                               const uint4 *cold, const kgx_call *calls, const uint32_t *otu_count,
+                               const kgx_otu *otus, kgx_hit *hits_out, kgx_call *calls_out, kgx_otu *otus_out,
+                               uint64_t *h0, uint64_t *h1, uint64_t *h2, const uint32_t *status,
+                               const kgx_best_call *best, kgx_best_call *best_host, uint32_t *status_host,
+                               uint64_t *nwin_host, uint32_t *done_host, uint32_t token, uint32_t *blocks_done,
+                               uint32_t hit_format, hipStream_t stream);
 hipError_t launch_gather(uint32_t n_seq, const uint64_t *wbase, const uint64_t *hit_mask,
                          uint32_t tile_windows, const uint32_t *call_count, const uint4 *hot, const uint4 *cold,
                          const kgx_call *calls, const uint64_t *hit_dense_off,
@@ -226,13 +250,6 @@ hipError_t launch_gather(uint32_t n_seq, const uint64_t *wbase, const uint64_t *
                          const uint64_t *otu_dense_off, kgx_otu *otus_out, hipStream_t stream,
                          uint4 *hits16_out = nullptr, /* PACKED16: the 16-B records, dense, instead of kgx_hit */
                          uint32_t *hits12_out = nullptr); /* PACKED16: 12-B records without the key */
-/* per-sequence OTU tallies in otus_by_count order at otus[window_base[s]] */
-hipError_t launch_otus(uint32_t n_seq, const uint64_t *wbase, const uint64_t *hit_mask, uint32_t tile_windows,
-                       const uint4 *hot, const uint4 *cold, int32_t *ws, kgx_otu *otus, uint32_t *otu_count,
-                       uint32_t hit_format, hipStream_t stream);
-/* find_best_call per sequence: calls[start[s] ..+ count[s]), ws same extent */
-hipError_t launch_best_calls(uint32_t n_seq, const kgx_call *calls, const uint64_t *start, const uint32_t *count,
-                             kgx_call *ws, kgx_best_call *out, hipStream_t stream);
 /* dense CSR offsets (n + 1 each) of up to three per-sequence count arrays
  * (NULL count array: all-zero offsets) */
 size_t count_scan_workspace_bytes(uint32_t n);
@@ -248,15 +265,57 @@ struct SmallPieces {
     uint64_t end16[SMALL_PIECES];
 };
 hipError_t launch_small_upload(const SmallPieces &pc, hipStream_t stream);
-/* small_collect + gather in one workgroup, for batches of up to
- * SMALL_GATHER_SEQ sequences (offsets into mapped h0..h2, records into the
- * mapped outputs; a NULL output is not gathered); last, token is stored to
- * mapped *done_host (when not NULL) after a system-scope fence, by the last
- * workgroup to finish (blocks_done: a zeroed device word the kernel leaves
- * zeroed; NULL = one workgroup) */
-/* one launch per small batch (kgx_fused.hip, context option "small_fused"):
- * one workgroup per sequence of at most FUSED_MAX_WINDOWS windows, results
- * stored straight into mapped host memory */
+hipError_t launch_small_collect(uint32_t n, const uint32_t *c0, const uint32_t *c1, const uint32_t *c2, uint64_t *o0,
+                                uint64_t *o1, uint64_t *o2, uint64_t *h0, uint64_t *h1, uint64_t *h2,
+                                const uint32_t *status, const uint64_t *wbase, const kgx_best_call *best,
+                                kgx_best_call *best_host, uint32_t *status_host, uint64_t *nwin_host,
+                                hipStream_t stream);
+/* one workgroup: launch_count_scan's offsets into o* (HBM) and h* (mapped
+ * host), plus status[0], wbase[n] and (best_host non-NULL) best[0, n) */
+hipError_t launch_small_collect_best(uint32_t n, const uint32_t *c0, const uint32_t *c1, const uint32_t *c2,
+                                     uint64_t *o0, uint64_t *o1, uint64_t *o2, uint64_t *h0, uint64_t *h1,
+                                     uint64_t *h2, const uint32_t *status, const uint64_t *wbase,
+                                     const kgx_call *calls, const uint32_t *call_count, kgx_call *ws,
+                                     kgx_best_call *best, kgx_best_call *best_host, uint32_t *status_host,
+                                     uint64_t *nwin_host, hipStream_t stream);
+/* min(*count, cap) elements of elem_bytes (a multiple of 4) from src to dst,
+ * both 16-byte aligned */
+hipError_t launch_copy_counted(void *dst, const void *src, const uint64_t *count, uint64_t cap,
+                               uint32_t elem_bytes, int blocks, hipStream_t stream);
+/* *flag_mapped = 1 when a byte of d[skip, n) is 0 (d 16-byte aligned) */
+hipError_t launch_nul_scan(const uint8_t *d, uint64_t skip, uint64_t n, uint32_t *flag_mapped, hipStream_t stream);
+
+/* device stores of bytes (4-aligned) from HBM into mapped pinned host memory */
+hipError_t launch_copy_to_host(void *dst_mapped, const void *src, uint64_t bytes, int blocks, hipStream_t stream);
+/* up to kMax copies device -> mapped host memory in one launch; add() takes
+ * byte counts (4-B aligned; 16-B aligned spans copy by 16 B) */
+struct CopySpans {
+    static constexpr int kMax = 8;
+    void *dst[kMax];
+    const void *src[kMax];
+    uint64_t n[kMax];
+    bool v16[kMax];
+    int count = 0;
+    void add(void *d, const void *s, uint64_t bytes)
+    {
+        if (bytes == 0)
+            return;
+        if (count == kMax) {
+            count = kMax + 1; /* refused by launch_copy_spans */
+            return;
+        }
+        dst[count] = d;
+        src[count] = s;
+        n[count] = bytes;
+        count++;
+    }
+};
+hipError_t launch_copy_spans(CopySpans spans, int copy_blocks, hipStream_t stream);
+
+/* ---- kgx_fused.hip: one launch per small batch, and the call service ---- */
+/* one launch per small batch (context option "small_fused"): one workgroup
+ * per sequence of at most FUSED_MAX_WINDOWS windows, results stored straight
+ * into mapped host memory */
 constexpr uint32_t FUSED_MAX_WINDOWS = 2048;
 constexpr uint32_t FUSED_MAX_SEQ = 4096;
 /* a batch of at most FUSED_INLINE_SEQ sequences and FUSED_INLINE_RES residues
@@ -266,10 +325,10 @@ constexpr uint32_t FUSED_MAX_SEQ = 4096;
 constexpr uint32_t FUSED_INLINE_SEQ = 32;
 constexpr uint32_t FUSED_INLINE_RES = 2048;
 hipError_t launch_fused_small(const uint8_t *res, const uint64_t *off, const uint64_t *wbase, uint32_t n,
-                              uint32_t want, const void *packed_table, uint64_t num_sigs, kgx_params prm,
+                              uint32_t want, const ProbeTable &t, kgx_params prm,
                               kgx_hit *hits, kgx_call *calls, uint32_t *counts, uint32_t *done, uint32_t token,
                               uint32_t max_windows, uint64_t *dbg, const uint64_t *h_off, const uint64_t *h_wbase,
-                              const uint8_t *h_res, uint32_t inline_res, hipStream_t stream, uint32_t home_shift = 0);
+                              const uint8_t *h_res, uint32_t inline_res, hipStream_t stream);
 /* resident call service (kgx_svc.cpp, svc_kernel in kgx_fused.hip): one
  * persistent workgroup per slot polls its slot's request word in mapped host
  * memory and runs fused_small_body on the slot's sequence; no launch per call.
@@ -313,66 +372,11 @@ static_assert(sizeof(SvcSlotHdr) == 64 && sizeof(SvcSlotOut) == 64 && sizeof(Svc
 /* slots workgroups on stream; each leaves life_ticks after its start (device
  * wall clock, 100 MHz) or on stop */
 hipError_t launch_svc(const SvcSlotHdr *hdr, SvcSlotOut *out, SvcSlotDbg *dbg, const uint8_t *res, kgx_hit *hits,
-                      kgx_call *calls, kgx_otu *otus, uint32_t slots, const void *packed_table, uint64_t num_sigs,
-                      uint64_t life_ticks, int quad_probe, hipStream_t stream, uint32_t home_shift = 0,
+                      kgx_call *calls, kgx_otu *otus, uint32_t slots, const ProbeTable &t,
+                      uint64_t life_ticks, int quad_probe, hipStream_t stream,
                       uint32_t poll_chunks = SVC_POLL_CHUNKS);
-constexpr uint32_t SMALL_GATHER_SEQ = 256;
-constexpr uint32_t SMALL_COLLECT_BEST_SEQ = 8192;
-constexpr uint32_t SMALL_GATHER_BLOCKS = 64; /* workgroups of the small gather (one wave per sequence) */
-hipError_t launch_small_gather(uint32_t n, const uint64_t *wbase, const uint64_t *hit_mask, uint32_t tile_windows,
-                               const uint32_t *hit_count, const uint32_t *call_count, const uint4 *hot,
-                               const uint4 *cold, const kgx_call *calls, const uint32_t *otu_count,
-                               const kgx_otu *otus, kgx_hit *hits_out, kgx_call *calls_out, kgx_otu *otus_out,
-                               uint64_t *h0, uint64_t *h1, uint64_t *h2, const uint32_t *status,
-                               const kgx_best_call *best, kgx_best_call *best_host, uint32_t *status_host,
-                               uint64_t *nwin_host, uint32_t *done_host, uint32_t token, uint32_t *blocks_done,
-                               uint32_t hit_format, hipStream_t stream);
-/* one workgroup: launch_count_scan's offsets into o* (HBM) and h* (mapped
- * host), plus status[0], wbase[n] and (best_host non-NULL) best[0, n) */
-hipError_t launch_small_collect_best(uint32_t n, const uint32_t *c0, const uint32_t *c1, const uint32_t *c2,
-                                     uint64_t *o0, uint64_t *o1, uint64_t *o2, uint64_t *h0, uint64_t *h1,
-                                     uint64_t *h2, const uint32_t *status, const uint64_t *wbase,
-                                     const kgx_call *calls, const uint32_t *call_count, kgx_call *ws,
-                                     kgx_best_call *best, kgx_best_call *best_host, uint32_t *status_host,
-                                     uint64_t *nwin_host, hipStream_t stream);
-hipError_t launch_small_collect(uint32_t n, const uint32_t *c0, const uint32_t *c1, const uint32_t *c2, uint64_t *o0,
-                                uint64_t *o1, uint64_t *o2, uint64_t *h0, uint64_t *h1, uint64_t *h2,
-                                const uint32_t *status, const uint64_t *wbase, const kgx_best_call *best,
-                                kgx_best_call *best_host, uint32_t *status_host, uint64_t *nwin_host,
-                                hipStream_t stream);
-/* min(*count, cap) elements of elem_bytes (a multiple of 4) from src to dst,
- * both 16-byte aligned */
-hipError_t launch_copy_counted(void *dst, const void *src, const uint64_t *count, uint64_t cap,
-                               uint32_t elem_bytes, int blocks, hipStream_t stream);
-/* *flag_mapped = 1 when a byte of d[skip, n) is 0 (d 16-byte aligned) */
-hipError_t launch_nul_scan(const uint8_t *d, uint64_t skip, uint64_t n, uint32_t *flag_mapped, hipStream_t stream);
 
-/* device stores of bytes (4-aligned) from HBM into mapped pinned host memory */
-/* up to kMax copies device -> mapped host memory in one launch; add() takes
- * byte counts (4-B aligned; 16-B aligned spans copy by 16 B) */
-struct CopySpans {
-    static constexpr int kMax = 8;
-    void *dst[kMax];
-    const void *src[kMax];
-    uint64_t n[kMax];
-    bool v16[kMax];
-    int count = 0;
-    void add(void *d, const void *s, uint64_t bytes)
-    {
-        if (bytes == 0)
-            return;
-        if (count == kMax) {
-            count = kMax + 1; /* refused by launch_copy_spans */
-            return;
-        }
-        dst[count] = d;
-        src[count] = s;
-        n[count] = bytes;
-        count++;
-    }
-};
-hipError_t launch_copy_spans(CopySpans spans, int copy_blocks, hipStream_t stream);
-hipError_t launch_copy_to_host(void *dst_mapped, const void *src, uint64_t bytes, int blocks, hipStream_t stream);
+/* ---- kgx_synth.hip: synthetic images and queries, the random-read probe ---- */
 hipError_t launch_random_read(const void *buffer, uint64_t bytes, uint64_t threads,
                               uint32_t rounds, int mode, int ilp, uint64_t *sink, hipStream_t stream);
 /* the synthetic spec of n_keys entries (its source proteins), the first

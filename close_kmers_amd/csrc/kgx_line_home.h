@@ -51,7 +51,8 @@ namespace kgx {
 
 constexpr uint32_t LINE_HOME_MOD = 0, LINE_HOME_MINIMIZER = 1;
 
-/* What the probe launchers take as `home_shift`: bits 0-7 the shift hs (a
+/* The home word, what the probe launchers take as ProbeTable.home
+ * (kgx_internal.h) and the kernels as `home`: bits 0-7 the shift hs (a
  * key's home bucket is home(key) << hs over num_sigs >> hs homes: 0 the
  * reference slots, 2 the 4-bucket lines of the index), bits 8-15 the
  * LINE_HOME_* mode of the image's index (0 where hs is 0), bit 16 set when

@@ -350,6 +350,22 @@ struct RollupScratch {
     bool enqueued = false;
 };
 
+/* kgx_image_set_line_index (kgx_line_index.hip): an image's PACKED16 records
+ * again, 4 buckets a line, each key's home at the start of its home line
+ * (line_home under `home`, kgx_line_home.h) */
+struct LineIndex {
+    packed_bucket *records = nullptr;
+    uint64_t n_lines = 0;
+    uint32_t home = LINE_HOME_MOD; /* the home mode it was built with */
+    bool marks = false; /* it carries overflow marks (KGX_LINE_MARKS, kgx_line_home.h) */
+    bool twins = false; /* it was built with twin records (KGX_LINE_TWINS, kgx_line_home.h) */
+    uint64_t n_twins = 0; /* how many: the keys with two home lines */
+    uint32_t load = 0; /* keys per 64 lines it was built for */
+    explicit operator bool() const { return records != nullptr; }
+    /* what its probes take as ProbeTable.home */
+    uint32_t home_word() const { return kgx::home_word(2u, home, marks, twins); }
+};
+
 }  // namespace kgx
 
 struct kgx_image {
@@ -358,17 +374,9 @@ struct kgx_image {
     int layout = KGX_LAYOUT_AOS24;
     kgx_sig_kmer *d_table = nullptr;   /* AOS24: the file's buckets */
     kgx::packed_bucket *d_packed = nullptr; /* PACKED16 */
-    /* kgx_image_set_line_index: the PACKED16 records again, 4 buckets a line,
-     * each key's home at the start of its home line (line_home under
-     * lines_home, kgx_line_home.h); the probes read it instead of d_packed,
-     * which stays for downloads, saves and filters */
-    kgx::packed_bucket *d_lines = nullptr;
-    uint64_t n_lines = 0;
-    uint32_t lines_home = kgx::LINE_HOME_MOD; /* the home mode it was built with */
-    bool lines_marks = false; /* it carries overflow marks (KGX_LINE_MARKS, kgx_line_home.h) */
-    bool lines_have_twins = false; /* it was built with twin records (KGX_LINE_TWINS, kgx_line_home.h) */
-    uint64_t lines_twins = 0; /* how many: the keys with two home lines */
-    uint32_t lines_load = 0; /* keys per 64 lines it was built for */
+    /* kgx_image_set_line_index: the probes read it instead of d_packed, which
+     * stays for downloads, saves and filters */
+    kgx::LineIndex lines;
     uint64_t *d_filter = nullptr;           /* presence filter (kgx_image_set_filter) */
     uint32_t filter_log2_words = 0;
     /* probe order across the image's contexts: the probe is bound by random
@@ -399,9 +407,12 @@ struct kgx_image {
         return num_sigs * (layout == KGX_LAYOUT_PACKED16 ? sizeof(kgx::packed_bucket) : sizeof(kgx_sig_kmer));
     }
     /* what the probes read: the line index when there is one */
-    const void *probe_table() const { return d_lines ? static_cast<const void *>(d_lines) : resident(); }
-    uint64_t probe_buckets() const { return d_lines ? 4 * n_lines : num_sigs; }
-    uint32_t home_shift() const { return d_lines ? kgx::home_word(2u, lines_home, lines_marks, lines_have_twins) : 0u; }
+    kgx::ProbeTable probe_table() const
+    {
+        return lines ? kgx::ProbeTable{lines.records, 4 * lines.n_lines, lines.home_word()} : reference_table();
+    }
+    /* the resident table under the reference's slots */
+    kgx::ProbeTable reference_table() const { return kgx::ProbeTable{resident(), num_sigs, 0u}; }
 };
 
 struct kgx_ctx {
@@ -533,14 +544,20 @@ struct kgx_ctx {
 namespace kgx {
 static_assert(CtxOptions{}.probe_variant == PROBE_AUTO && CtxOptions{}.probe_j == PROBE_J_DEFAULT,
               "kgx_options.h spells these two defaults as numbers");
-/* what c's probes read: the image's line index unless option "line_index" is 0 */
-inline bool ctx_lines(const kgx_ctx *c) { return c->img->d_lines && c->opt.line_index; }
-inline const void *ctx_probe_table(const kgx_ctx *c)
+/* drops the image's line index, if any (the caller has set the device and
+ * knows no kernel reads it) */
+inline void drop_line_index(kgx_image *img)
 {
-    return ctx_lines(c) ? static_cast<const void *>(c->img->d_lines) : c->img->resident();
+    if (img->lines)
+        (void)hipFree(img->lines.records);
+    img->lines = LineIndex{};
 }
-inline uint64_t ctx_probe_buckets(const kgx_ctx *c) { return ctx_lines(c) ? 4 * c->img->n_lines : c->img->num_sigs; }
-inline uint32_t ctx_home_shift(const kgx_ctx *c) { return ctx_lines(c) ? c->img->home_shift() : 0u; }
+/* what c's probes read: the image's line index unless option "line_index" is 0 */
+inline bool ctx_lines(const kgx_ctx *c) { return c->img->lines && c->opt.line_index; }
+inline ProbeTable ctx_probe_table(const kgx_ctx *c)
+{
+    return ctx_lines(c) ? c->img->probe_table() : c->img->reference_table();
+}
 /* a host batch's result: the context's host arrays */
 inline void fill_result(kgx_ctx *c, uint32_t n_seq, bool need_hits, bool want_best, uint64_t nwin, kgx_result *out)
 {

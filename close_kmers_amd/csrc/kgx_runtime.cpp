@@ -805,8 +805,7 @@ int kgx_image_close(kgx_image *img)
         (void)hipFree(img->d_table);
     if (img->d_packed)
         (void)hipFree(img->d_packed);
-    if (img->d_lines)
-        (void)hipFree(img->d_lines);
+    drop_line_index(img);
     if (img->d_filter)
         (void)hipFree(img->d_filter);
     if (img->probe_stream) {
@@ -861,150 +860,14 @@ int kgx_image_set_layout(kgx_image *img, int layout)
     if (layout == KGX_LAYOUT_PACKED16)
         return image_pack(img);
     if (layout == KGX_LAYOUT_AOS24) {
-        if (img->d_lines) { /* the line index holds PACKED16 records */
+        if (img->lines) { /* the line index holds PACKED16 records */
             HIP_TRY(hipSetDevice(img->device));
             HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(img->d_lines);
-            img->d_lines = nullptr;
-            img->n_lines = 0;
+            drop_line_index(img);
         }
         return image_unpack(img);
     }
     return fail(KGX_EINVAL, "unknown layout " + std::to_string(layout));
-}
-
-int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
-{
-    if (!img)
-        return fail(KGX_EINVAL, "null image");
-    if (keys_per_64_lines > 255)
-        return fail(KGX_EINVAL, "line index load: 0 (none) or 1 .. 255 keys per 64 lines");
-    /* the home of a key in this index: KGX_LINE_HOME 1 = the minimizer home
-     * (the default), 0 = key mod n_lines (kgx_line_home.h); read at each
-     * call, a property of the index it builds */
-    uint32_t home_mode = kgx::LINE_HOME_MINIMIZER;
-    if (const char *v = getenv("KGX_LINE_HOME")) {
-        if (!strcmp(v, "0"))
-            home_mode = kgx::LINE_HOME_MOD;
-        else if (strcmp(v, "1") && *v)
-            return fail(KGX_EINVAL, std::string("KGX_LINE_HOME: 0 (mod) or 1 (minimizer), not \"") + v + "\"");
-    }
-    /* overflow marks on the index's full lines, which end an absent key's
-     * chain in one line (kgx_line_home.h): KGX_LINE_MARKS 1 (the default)
-     * builds them, 0 builds none; read at each call like KGX_LINE_HOME */
-    bool marks = true;
-    if (const char *v = getenv("KGX_LINE_MARKS")) {
-        if (!strcmp(v, "0"))
-            marks = false;
-        else if (strcmp(v, "1") && *v)
-            return fail(KGX_EINVAL, std::string("KGX_LINE_MARKS: 0 (none) or 1 (marks), not \"") + v + "\"");
-    }
-    /* twin records, which let two neighbouring windows always share a line
-     * (kgx_line_home.h): KGX_LINE_TWINS 1 (the default) builds them where the
-     * rule of kgx.h allows, 0 builds none; read at each call like the two above */
-    bool twins = home_mode == kgx::LINE_HOME_MINIMIZER && marks && keys_per_64_lines <= KGX_LINE_TWINS_MAX_LOAD;
-    if (const char *v = getenv("KGX_LINE_TWINS")) {
-        if (!strcmp(v, "0"))
-            twins = false;
-        else if (strcmp(v, "1") && *v)
-            return fail(KGX_EINVAL, std::string("KGX_LINE_TWINS: 0 (none) or 1 (twins), not \"") + v + "\"");
-    }
-    /* the service's workgroups hold the probe table's address */
-    const auto hold = svc_shutdown_hold(img);
-    HIP_TRY(hipSetDevice(img->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (img->d_lines)
-        (void)hipFree(img->d_lines);
-    img->d_lines = nullptr;
-    img->n_lines = 0;
-    img->lines_twins = 0;
-    if (!keys_per_64_lines)
-        return KGX_OK;
-    if (img->layout != KGX_LAYOUT_PACKED16)
-        return fail(KGX_EINVAL, "a line index needs a PACKED16 image");
-    unsigned long long *d_count = nullptr; /* stored keys, twin records, the overflow flag */
-    uint32_t *d_over = nullptr;
-    HIP_TRY(hipMalloc(&d_count, 24));
-    d_over = reinterpret_cast<uint32_t *>(d_count + 2);
-    hipError_t e = hipMemset(d_count, 0, 24);
-    if (e == hipSuccess)
-        e = launch_count_keys(img->d_packed, img->num_sigs, d_count, nullptr);
-    unsigned long long n_keys = 0;
-    if (e == hipSuccess)
-        e = hipMemcpy(&n_keys, d_count, 8, hipMemcpyDeviceToHost);
-    /* lines: n_keys * 64 / load, odd and prime to 5 (keys are base-20 codes) */
-    uint64_t n_lines = std::max<uint64_t>(1, (uint64_t)(((unsigned __int128)n_keys * 64 + keys_per_64_lines - 1) /
-                                                        keys_per_64_lines));
-    while (n_lines % 2 == 0 || n_lines % 5 == 0)
-        n_lines++;
-    packed_bucket *lines = nullptr;
-    if (e == hipSuccess && (4 * n_lines >= (1ull << 40) || hipMalloc(&lines, 4 * n_lines * sizeof(packed_bucket)) != hipSuccess)) {
-        (void)hipGetLastError();
-        (void)hipFree(d_count);
-        return fail(KGX_ENOMEM, "no room for the line index (" + std::to_string(4 * n_lines * 16) + " B)");
-    }
-    uint32_t over = 0;
-    unsigned long long n_twins = 0;
-    if (e == hipSuccess)
-        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, marks, twins, d_over,
-                               d_count + 1, nullptr);
-    if (e == hipSuccess)
-        e = hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        e = hipMemcpy(&n_twins, d_count + 1, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_count);
-    if (e != hipSuccess || over) {
-        if (lines)
-            (void)hipFree(lines);
-        return fail(KGX_EDEVICE, e != hipSuccess ? std::string("line index: ") + hipGetErrorString(e)
-                                                 : std::string("line index: a record found no bucket"));
-    }
-    img->d_lines = lines;
-    img->n_lines = n_lines;
-    img->lines_home = home_mode;
-    img->lines_marks = marks;
-    img->lines_twins = n_twins;
-    img->lines_have_twins = twins;
-    img->lines_load = keys_per_64_lines;
-    return KGX_OK;
-}
-
-uint64_t kgx_image_line_count(const kgx_image *img) { return img ? img->n_lines : 0; }
-uint32_t kgx_image_line_home(const kgx_image *img) { return img && img->d_lines ? img->lines_home : 0; }
-uint64_t kgx_image_line_twins(const kgx_image *img) { return img && img->d_lines ? img->lines_twins : 0; }
-
-int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
-{
-    if (!img || !out)
-        return fail(KGX_EINVAL, "null image or output");
-    if (!img->d_lines)
-        return fail(KGX_EINVAL, "the image has no line index");
-    HIP_TRY(hipSetDevice(img->device));
-    /* the marks the stored records call for, 16 bits a line, and 8 counters */
-    const uint64_t words = (img->n_lines + 1) / 2;
-    uint32_t *d_scratch = nullptr;
-    if (hipMalloc(&d_scratch, words * 4 + 64) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KGX_ENOMEM, "no room for the line statistics (" + std::to_string(words * 4) + " B)");
-    }
-    unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_scratch);
-    hipError_t e = hipMemset(d_scratch, 0, words * 4 + 64);
-    if (e == hipSuccess)
-        e = launch_lines_stats(img->d_lines, img->n_lines, img->lines_home, img->lines_have_twins, d_scratch + 16,
-                               d_stats, nullptr);
-    unsigned long long h[8] = {};
-    if (e == hipSuccess)
-        e = hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d_scratch);
-    if (e != hipSuccess)
-        return fail(KGX_EDEVICE, std::string("line statistics: ") + hipGetErrorString(e));
-    for (int i = 0; i < 8; i++)
-        out[i] = h[i];
-    if (img->lines_have_twins) { /* counted in halves, per key (lines_mark_kernel) */
-        out[0] /= 2;
-        out[1] /= 2;
-    }
-    return KGX_OK;
 }
 
 /* buckets [first, first + count) in the file's format into host memory */
@@ -1352,9 +1215,9 @@ int stage_probe_dna(kgx_ctx *c, const uint8_t *bases, uint64_t n_bases, const ui
                                 "(set fq_residues 1 for other probes)");
     return probe_chained(c, [&] {
         return launch_probe_dna(bases, n_bases, anchors, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(),
-                                c->n_seq, c->max_tiles, ctx_probe_table(c), ctx_probe_buckets(c),
+                                c->n_seq, c->max_tiles, ctx_probe_table(c),
                                 c->hits.as<uint4>(), c->hit_mask.as<uint64_t>(), (int)(c->tile_windows / 64),
-                                probe_max_blocks(c), c->stream, ctx_home_shift(c));
+                                probe_max_blocks(c), c->stream);
     });
 }
 
@@ -1368,11 +1231,11 @@ int kgx_stage_probe(kgx_ctx *c, const uint8_t *d_res, const uint64_t *d_off)
         return fail(KGX_EINVAL, "probe: residues missing or offsets differ from the plan");
     return probe_chained(c, [&] {
         return launch_probe(d_res, c->n_residues, d_off, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(),
-                            c->n_seq, c->max_tiles, ctx_probe_table(c), c->img->layout, ctx_probe_buckets(c),
+                            c->n_seq, c->max_tiles, ctx_probe_table(c), c->img->layout,
                             c->opt.probe_filter ? c->img->d_filter : nullptr, c->img->filter_log2_words,
                             c->hits.as<uint4>(), c->hits.as<uint4>() + c->hit_slots, c->hit_mask.as<uint64_t>(),
                             (int)(c->tile_windows / 64), c->opt.probe_variant, (uint32_t)c->opt.probe_lds_kb,
-                            probe_max_blocks(c), c->stream, ctx_home_shift(c), (uint32_t)c->opt.probe_nt);
+                            probe_max_blocks(c), c->stream, (uint32_t)c->opt.probe_nt);
     });
 }
 

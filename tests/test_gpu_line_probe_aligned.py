@@ -1,4 +1,4 @@
-"""The line probe's aligned slice body (probe_slice_aligned, csrc/kgx_lookup.hip),
+"""The line probe's aligned slice body (probe_slice_aligned, csrc/kgx_probe.hip),
 which every index with marks runs: 32-bit line numbers, the key handed to the
 quad as its low word and a word that packs key bits 32-34 with the open-chain
 bit and the key's mark, and the home taken from the two 7-mers the encode
