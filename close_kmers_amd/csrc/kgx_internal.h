@@ -179,8 +179,12 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
                         uint64_t max_tiles, const ProbeTable &t, int layout,
                         const uint64_t *filter, uint32_t filter_log2_words,
                         uint4 *hot, uint4 *cold, uint64_t *hit_mask, int probe_j, int variant,
-                        uint32_t lds_kb, uint32_t max_blocks, hipStream_t stream, uint32_t nt_stores = 0);
-/* nt_stores 1: the line probe writes its hit records and mask words with
+                        uint32_t lds_kb, uint32_t max_blocks, bool defer, hipStream_t stream,
+                        uint32_t nt_stores = 0);
+/* defer: over an aligned index with marks the line probe runs each slice's
+ * first round and then the tile's open chains together, 16 to a load
+ * instruction (a context's KGX_PROBE_DEFER); false: rounds per slice.
+ * nt_stores 1: the line probe writes its hit records and mask words with
  * non-temporal stores (context option "probe_nt", an A/B knob).
  * max_blocks > 0 caps the line probe's grid (its waves then stride over the
  * tiles; option probe_persist); 0 = one workgroup per 4 tiles.
@@ -189,7 +193,7 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
  * launch_probe over the translated residues (HIT_PACKED16 records) */
 hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64_t *anchor, const uint64_t *wbase,
                             const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const ProbeTable &t,
-                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks,
+                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks, bool defer,
                             hipStream_t stream);
 
 /* ---- kgx_line_index.hip: the resident layouts and the presence filter ---- */

@@ -492,7 +492,122 @@ __device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ pa
     }
 }
 
-template <int J, int G, bool DNA, bool MARKS, bool TWINS>
+/*
+ * The deferred form of the aligned slice (DEFER, the default; environment
+ * switch KGX_PROBE_DEFER): a tile's chains that leave their first line are not
+ * walked slice by slice, a few lanes at a time at the whole round's cost, but
+ * once for the tile, packed 16 to a load instruction.
+ *
+ * quad_line_word is probe_slice_aligned's test of one line: the quad's word
+ * (bit c: record c holds the key or is empty; bit G: the line carries the
+ * key's mark; 0 for a closed chain) and `diff`, 0 where this lane's record
+ * holds the key.
+ */
+__device__ __forceinline__ uint32_t quad_line_word(const uint4 &d, uint32_t klo, uint32_t kw, bool open,
+                                                   uint32_t cbit, uint32_t &diff)
+{
+    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32), MARKED = 1u << 4;
+    constexpr uint32_t MAX_HI = (uint32_t)(MAX_ENCODED >> 32), MAX_LO = (uint32_t)MAX_ENCODED;
+    const uint32_t kh = d.y & KEY_HI;
+    diff = (d.x ^ klo) | ((d.y ^ kw) & KEY_HI);
+    const bool ends = diff == 0 || kh > MAX_HI || (kh == MAX_HI && d.x > MAX_LO);
+    uint32_t w = (ends ? cbit : 0u) | ((d.w & kw) >= 1u << 28 ? MARKED : 0u);
+    w = open ? w : 0u;
+    w |= (uint32_t)xor_lane((int32_t)w, 1);
+    w |= (uint32_t)xor_lane((int32_t)w, 2);
+    return w;
+}
+
+/* Round 0 of a 64-window slice, straight-line: probe_slice_aligned's hand-over
+ * and one round of it without the loop.  Returns the quad's open chains, bit i
+ * for instruction i (the same in the quad's four lanes); their next line is
+ * the one after the home. */
+__device__ __forceinline__ uint32_t probe_slice_round0(const uint4 *__restrict__ packed, uint64_t key, uint32_t own,
+                                                       uint32_t home_line, uint32_t q, uint32_t c, uint4 *rec,
+                                                       uint8_t *hitf)
+{
+    constexpr uint32_t G = 4, NQ = 64 / G, MARKED = 1u << G;
+    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+    uint32_t klo[G], kw[G], ln[G];
+    uint32_t live = 0;
+#pragma unroll
+    for (int i = 0; i < (int)G; i++) {
+        const int owner = (int)(NQ * i + q);
+        klo[i] = (uint32_t)__shfl((int)(uint32_t)key, owner);
+        ln[i] = (uint32_t)__shfl((int)home_line, owner);
+        const uint32_t o = (uint32_t)__shfl((int)own, owner);
+        live |= (o >> 3 & 1u) << i;
+        const uint32_t g = o >> 4;
+        kw[i] = (o & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+    }
+    const uint32_t cbit = 1u << c, upto = (2u << c) - 1u;
+    uint4 d[G];
+#pragma unroll
+    for (int i = 0; i < (int)G; i++)
+        if (live >> i & 1u)
+            d[i] = packed[(uint64_t)ln[i] * G + c];
+    uint32_t hitm = 0;
+#pragma unroll
+    for (int i = 0; i < (int)G; i++) {
+        uint32_t diff;
+        const uint32_t w = quad_line_word(d[i], klo[i], kw[i], live >> i & 1u, cbit, diff);
+        hitm |= diff == 0 && (w & upto) == cbit ? 1u << i : 0u;
+        live = (w & (2u * MARKED - 1)) == MARKED ? live : live & ~(1u << i);
+    }
+#pragma unroll
+    for (int i = 0; i < (int)G; i++)
+        if (hitm >> i & 1u) {
+            rec[NQ * i + q] = d[i];
+            hitf[NQ * i + q] = 1;
+        }
+    return live;
+}
+
+/* The tile's n_open chains left open by round 0, in window order in `list`
+ * (window slots of the tile); chain w's entry lies in rec[w], which is free
+ * until the chain hits: key low word, the owner's word of probe_slice_aligned
+ * (key bits 32-34, line_mark from bit 4), next line.  Quad q walks entry
+ * 16 p + q of pass p, all 16 in one load instruction per round, by
+ * probe_slice_aligned's rules; a chain has visited one line already, so the
+ * rounds count from 1 towards the n_lines + 2 that cover the table. */
+__device__ __forceinline__ void probe_tile_deferred(const uint4 *__restrict__ packed, uint32_t n_lines,
+                                                    uint32_t n_open, const uint8_t *list, uint32_t q, uint32_t c,
+                                                    uint4 *rec, uint8_t *hitf)
+{
+    constexpr uint32_t G = 4, NQ = 64 / G, MARKED = 1u << G;
+    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+    const uint32_t cbit = 1u << c, upto = (2u << c) - 1u;
+    const uint32_t max_lines = n_lines + 2;
+    for (uint32_t p = 0; p < n_open; p += NQ) {
+        bool live = p + q < n_open;
+        uint32_t w = 0;
+        uint4 e = make_uint4(0, 0, 0, 0);
+        if (live) {
+            w = list[p + q];
+            e = rec[w];
+        }
+        const uint32_t klo = e.x, g = e.y >> 4;
+        const uint32_t kw = (e.y & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+        uint32_t ln = e.z;
+        for (uint32_t round = 1;; round++) {
+            uint4 d; /* fresh each round, as in probe_slice_aligned */
+            if (live)
+                d = packed[(uint64_t)ln * G + c];
+            uint32_t diff;
+            const uint32_t lw = quad_line_word(d, klo, kw, live, cbit, diff);
+            if (diff == 0 && (lw & upto) == cbit) {
+                rec[w] = d;
+                hitf[w] = 1;
+            }
+            live = live && (lw & (2u * MARKED - 1)) == MARKED && round + 1 < max_lines;
+            ln = ln + 1 == n_lines ? 0 : ln + 1;
+            if (!__any(live))
+                break;
+        }
+    }
+}
+
+template <int J, int G, bool DNA, bool MARKS, bool TWINS, bool DEFER>
 __global__ __launch_bounds__(256) void probe_line_kernel(
     const uint8_t *__restrict__ residues, uint64_t n_residues, const uint64_t *__restrict__ seq_off,
     const uint64_t *__restrict__ wbase, const uint32_t *__restrict__ tile_seq, uint32_t n_seq,
@@ -505,6 +620,8 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
     __shared__ uint8_t cod_tab[DNA ? 68 : 1];
     __shared__ uint4 lds_rec[PROBE_WAVES][T];
     __shared__ uint8_t lds_hit[PROBE_WAVES][T];
+    __shared__ uint8_t lds_open[PROBE_WAVES][DEFER ? T : 1]; /* DEFER: the tile's open chains (window slots) */
+    static_assert(T <= 256, "a window slot is a byte of lds_open");
     if (DNA) {
         const uint32_t b = threadIdx.x | 0x20u; /* ACGTU either case (trans_table.h:45-68) */
         const bool base = b == 'a' || b == 'c' || b == 'g' || b == 't' || b == 'u';
@@ -559,11 +676,40 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
                 home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(home)) : 0;
             lds_hit[wave][64 * j + lane] = 0;
         }
+        if constexpr (DEFER) {
+            /* each slice's first round, then the tile's open chains together.
+             * A window's owner learns from its quad (lanes 4 (l % 16) on,
+             * instruction l / 16) whether the chain is open and files it: the
+             * ballot is in window order, so under TWINS an even window and
+             * its successor are neighbouring quads of a deferred instruction
+             * too (unless a pass boundary parts them) and ask for one line */
+            uint32_t n_open = 0; /* per tile: a wave may walk many */
+#pragma unroll
+            for (int j = 0; j < J; j++) {
+                const uint32_t own = (uint32_t)(key[j] >> 32) | (uint32_t)ok[j] << 3 | line_mark(key[j]) << 4;
+                const uint32_t live = probe_slice_round0(packed, key[j], own, home_line[j], q, c,
+                                                         &lds_rec[wave][64 * j], &lds_hit[wave][64 * j]);
+                const uint32_t of_quad = (uint32_t)__shfl((int)live, (int)(G * (lane % NQ)));
+                const bool open = of_quad >> (lane / NQ) & 1u;
+                const uint64_t m = __ballot(open);
+                if (open) {
+                    const uint32_t next = home_line[j] + 1 == n_lines ? 0 : home_line[j] + 1;
+                    lds_rec[wave][64 * j + lane] = make_uint4((uint32_t)key[j], own, next, 0);
+                    lds_open[wave][n_open + lanes_below(m)] = (uint8_t)(64 * j + lane);
+                }
+                n_open += (uint32_t)__popcll(m);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            probe_tile_deferred(packed, n_lines, n_open, lds_open[wave], q, c, lds_rec[wave], lds_hit[wave]);
+        } else {
         /* one 64-window slice at a time, as below */
 #pragma unroll
         for (int j = 0; j < J; j++)
             probe_slice_aligned(packed, n_lines, key[j], ok[j], home_line[j], q, c, &lds_rec[wave][64 * j],
                                 &lds_hit[wave][64 * j]);
+        }
     } else {
     if (DNA)
         encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, cod_tab,
@@ -664,16 +810,22 @@ template <int J, int G, bool DNA = false>
 static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *residues, uint64_t n_residues,
                               const uint64_t *seq_off, const uint64_t *wbase, const uint32_t *tile_seq,
                               uint32_t n_seq, const ProbeTable &t, uint4 *hot, uint4 *cold, uint64_t *hit_mask,
-                              uint32_t dyn_lds, uint32_t nt = 0)
+                              uint32_t dyn_lds, bool defer, uint32_t nt = 0)
 {
     /* the aligned slice body, with the mark test, only over an aligned index
      * (kgx_line_home.h); every other table runs the generic kernel, which
-     * ignores marks and stays exact */
-    auto *kernel = probe_line_kernel<J, G, DNA, false, false>;
+     * ignores marks and stays exact.  `defer` picks the aligned body's form,
+     * both compiled: no uniform branch stands in a round */
+    auto *kernel = probe_line_kernel<J, G, DNA, false, false, false>;
     if constexpr (G == 4)
-        if (line_index_aligned(t.num_sigs, t.home))
-            kernel = home_twins_of(t.home) ? probe_line_kernel<J, G, DNA, true, true>
-                                           : probe_line_kernel<J, G, DNA, true, false>;
+        if (line_index_aligned(t.num_sigs, t.home)) {
+            if (defer)
+                kernel = home_twins_of(t.home) ? probe_line_kernel<J, G, DNA, true, true, true>
+                                               : probe_line_kernel<J, G, DNA, true, false, true>;
+            else
+                kernel = home_twins_of(t.home) ? probe_line_kernel<J, G, DNA, true, true, false>
+                                               : probe_line_kernel<J, G, DNA, true, false, false>;
+        }
     hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues, n_residues, seq_off, wbase,
                        tile_seq, n_seq, static_cast<const uint4 *>(t.buckets), t.num_sigs, t.magic(), t.home, hot,
                        cold, hit_mask, nt);
@@ -721,7 +873,7 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
                         uint64_t max_tiles, const ProbeTable &t, int layout,
                         const uint64_t *filter, uint32_t filter_log2,
                         uint4 *hot, uint4 *cold, uint64_t *hit_mask, int probe_j, int variant,
-                        uint32_t lds_kb, uint32_t max_blocks, hipStream_t stream, uint32_t nt)
+                        uint32_t lds_kb, uint32_t max_blocks, bool defer, hipStream_t stream, uint32_t nt)
 {
     if (max_tiles == 0)
         return hipSuccess;
@@ -729,8 +881,10 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
         return hipErrorInvalidValue; /* line-aligned homes exist for PACKED16 records only */
     /* lds_kb > 0: each probe workgroup reserves that much LDS (unused beyond
      * its own ~9 KB), capping the probe at 160 / lds_kb workgroups per CU so
-     * that other contexts' kernels find room beside it */
-    const uint32_t dyn_lds = lds_kb * 1024u > 9216u ? lds_kb * 1024u - 9216u : 0u;
+     * that other contexts' kernels find room beside it; the deferred form's
+     * list of open chains adds 512 B to a 128-window tile's 8960 */
+    const uint32_t own_lds = defer ? 9728u : 9216u;
+    const uint32_t dyn_lds = lds_kb * 1024u > own_lds ? lds_kb * 1024u - own_lds : 0u;
     const dim3 grid((uint32_t)((max_tiles + PROBE_WAVES - 1) / PROBE_WAVES));
     /* the line probe strides over tiles when its grid is capped */
     const dim3 lgrid(max_blocks ? std::min<uint32_t>(grid.x, max_blocks) : grid.x);
@@ -739,7 +893,7 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
     if ((variant == PROBE_LINE || variant == PROBE_LINE8) && layout == KGX_LAYOUT_PACKED16 && !filter) {
 #define KGX_LINE(JJ, GG)                                                                             \
     launch_probe_line<JJ, GG>(lgrid, stream, residues, n_residues, seq_off, wbase, tile_seq, n_seq, t,  \
-                              hot, cold, hit_mask, dyn_lds, nt);                                     \
+                              hot, cold, hit_mask, dyn_lds, defer, nt);                              \
     return hipGetLastError()
         const int key = probe_j * 10 + (variant == PROBE_LINE8 ? 8 : 4);
         switch (key) {
@@ -774,7 +928,7 @@ hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint
 
 hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64_t *anchor, const uint64_t *wbase,
                             const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const ProbeTable &t,
-                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks,
+                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks, bool defer,
                             hipStream_t stream)
 {
     if (max_tiles == 0)
@@ -783,7 +937,7 @@ hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64
     const dim3 grid(max_blocks ? std::min<uint32_t>(tiles_grid, max_blocks) : tiles_grid);
 #define KGX_DNA(JJ)                                                                                  \
     launch_probe_line<JJ, 4, true>(grid, stream, bases, n_bases, anchor, wbase, tile_seq, n_seq, t,  \
-                                   hot, nullptr, hit_mask, 0);                                       \
+                                   hot, nullptr, hit_mask, 0, defer);                                \
     return hipGetLastError()
     switch (probe_j) {
     case 1: KGX_DNA(1);

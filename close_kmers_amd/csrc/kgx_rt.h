@@ -466,6 +466,7 @@ struct kgx_ctx {
     kgx::PinnedVec<uint64_t> h_fqc_tot, h_fqc_fo, h_fqc_coff;
     kgx::PinnedVec<kgx_call> h_fqc_calls;
     kgx::CtxOptions opt; /* the tuning options (kgx_ctx_set_option; kgx_options.h) */
+    bool probe_defer = true; /* KGX_PROBE_DEFER at creation: the line probe's deferred form (kgx_probe.hip) */
     /* host results */
     std::vector<uint64_t> h_hoff, h_coff, h_ooff;
     kgx::PinnedVec<kgx_hit> h_hits;

@@ -935,8 +935,19 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
     if (!img || !out)
         return fail(KGX_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(img->device));
+    /* KGX_PROBE_DEFER: the form of the line probe's aligned body for this
+     * context (kgx_probe.hip): 1 or unset, a tile's chains past their first
+     * line run once, packed, after every slice's first round; 0, each slice
+     * runs its own rounds.  An A/B switch, read here like KGX_SMALL_BATCH */
+    bool probe_defer = true;
+    if (const char *pd = std::getenv("KGX_PROBE_DEFER"); pd && *pd) {
+        if (std::strcmp(pd, "0") && std::strcmp(pd, "1"))
+            return fail(KGX_EINVAL, std::string("KGX_PROBE_DEFER: 0 (rounds per slice) or 1 (deferred), not \"") + pd + "\"");
+        probe_defer = pd[0] == '1';
+    }
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
+    c->probe_defer = probe_defer;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -1217,7 +1228,7 @@ int stage_probe_dna(kgx_ctx *c, const uint8_t *bases, uint64_t n_bases, const ui
         return launch_probe_dna(bases, n_bases, anchors, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(),
                                 c->n_seq, c->max_tiles, ctx_probe_table(c),
                                 c->hits.as<uint4>(), c->hit_mask.as<uint64_t>(), (int)(c->tile_windows / 64),
-                                probe_max_blocks(c), c->stream);
+                                probe_max_blocks(c), c->probe_defer, c->stream);
     });
 }
 
@@ -1235,7 +1246,7 @@ int kgx_stage_probe(kgx_ctx *c, const uint8_t *d_res, const uint64_t *d_off)
                             c->opt.probe_filter ? c->img->d_filter : nullptr, c->img->filter_log2_words,
                             c->hits.as<uint4>(), c->hits.as<uint4>() + c->hit_slots, c->hit_mask.as<uint64_t>(),
                             (int)(c->tile_windows / 64), c->opt.probe_variant, (uint32_t)c->opt.probe_lds_kb,
-                            probe_max_blocks(c), c->stream, (uint32_t)c->opt.probe_nt);
+                            probe_max_blocks(c), c->probe_defer, c->stream, (uint32_t)c->opt.probe_nt);
     });
 }
 

@@ -438,6 +438,12 @@ int kgx_sig_stage_ms(const kgx_sig *s, float *ms);
 int kgx_sig_destroy(kgx_sig *s);
 
 /* ---- contexts: one per host thread, like one KmerGuts per pool thread --- */
+/* The environment variable KGX_PROBE_DEFER, read when a context is created,
+ * picks the form of its line probe over a line index with marks: 1 or unset,
+ * every 64-window slice runs its first round and the tile's chains that left
+ * their first line are then walked together, 16 to a load instruction; 0,
+ * each slice runs all its rounds itself.  Same results either way (an A/B
+ * switch); any other value is KGX_EINVAL and no context is made. */
 int kgx_ctx_create(kgx_image *img, kgx_ctx **out);
 int kgx_ctx_destroy(kgx_ctx *ctx);
 /* the HIP stream the context launches on (hipStream_t) */

@@ -32,6 +32,14 @@ lines per absent key, and requests per window under two models of merging
 line a tile's windows touch is asked for once), and the fraction of lines that
 are full and were ever passed, the only ones a mark can sit on.
 
+For the twins rows it also counts the line probe's rounds (round_stats): the
+share of 64-window slices whose longest chain has 2, 3, 4 or more lines, the
+chains a 128-window tile has open after every window's first line (mean, and
+how often more than the 16 that one load instruction serves), and the rounds
+and dependent round trips per tile when each slice walks its own chains
+against one first round per slice and the tile's open chains walked together
+afterwards (KGX_PROBE_DEFER).
+
 The benchmark's image has 20^7 = 1.28e9 7-mers, 1.0e9 keys (a quarter of them
 consecutive windows of source proteins, as synth.py plants them) and 1.78e9
 lines: 0.78 keys and 1.39 lines per 7-mer.  The model keeps those two ratios
@@ -177,6 +185,40 @@ def tile_requests(qh, q_lines, n_lines, tile=128):
     return len(np.unique(touched)) / len(h)
 
 
+def round_stats(ql, slice_w=64, tile=128, quads=16):
+    """The line probe's rounds over the batch's windows in order (ql: lines per
+    window).  A 64-window slice that walks its own chains runs as many rounds
+    as its longest chain has lines.  The deferred form (KGX_PROBE_DEFER) runs
+    one round per slice and then the tile's open chains, in window order, 16
+    to a load instruction: a pass of 16 runs as many one-instruction rounds
+    as its longest chain has lines past the first."""
+    n = ql.ravel()
+    n = n[:len(n) // tile * tile]
+    per_slice = n.reshape(-1, slice_w).max(axis=1)
+    t = n.reshape(-1, tile)
+    opened = (t > 1).sum(axis=1)
+    deferred = np.zeros(len(t), np.int64)  # one-instruction rounds after the slices' first rounds
+    passes = np.zeros(len(t), np.int64)
+    for i, row in enumerate(t):
+        rest = row[row > 1] - 1
+        for p in range(0, len(rest), quads):
+            deferred[i] += rest[p:p + quads].max()
+            passes[i] += 1
+    slices = tile // slice_w
+    return {
+        "slices_with_2_rounds_or_more": float((per_slice >= 2).mean()),
+        "slices_with_3_rounds_or_more": float((per_slice >= 3).mean()),
+        "slices_with_4_rounds_or_more": float((per_slice >= 4).mean()),
+        "slice_rounds_per_tile": float(per_slice.reshape(-1, slices).sum(axis=1).mean()),
+        "open_chains_per_tile_after_round_0": float(opened.mean()),
+        "tiles_with_more_than_16_open_chains": float((opened > quads).mean()),
+        "deferred_passes_per_tile": float(passes.mean()),
+        "deferred_rounds_per_tile": float(deferred.mean()),
+        "dependent_round_trips_per_tile": {"per_slice": float(per_slice.reshape(-1, slices).sum(axis=1).mean()),
+                                           "deferred": float(slices + deferred.mean())},
+    }
+
+
 def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
     """the minimizer index with twin records, probed by the even/odd choice;
     the columns of the other two homes"""
@@ -229,6 +271,7 @@ def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
             "lines_marked": float((mk != 0).mean()),
             "mark_bits_per_marked_line": float(np.array([bin(int(v)).count("1") for v in mk[mk != 0][:100000]]).mean())
             if (mk != 0).any() else 0.0,
+            "rounds": round_stats(ql),
         }
     q0 = variants["0"]
     return {
@@ -367,6 +410,10 @@ def main():
             print(f"    {bits:>4s}  {v['query_lines_per_window']:12.4f}  {v['query_windows_past_first_line']:15.2%}  "
                   f"{v['lines_per_absent_key']:16.4f}  {v['query_requests_per_window']:.4f} / "
                   f"{v['query_requests_per_window_tile_merge']:.4f}")
+        if "rounds" in m["marks"]["16"]:
+            print("  the line probe's rounds, 16 mark bits (a 128-window tile of two 64-window slices):")
+            for k, v in m["marks"]["16"]["rounds"].items():
+                print(f"    {k:38s} {v:.4f}" if isinstance(v, float) else f"    {k:38s} {v}")
 
 
 if __name__ == "__main__":
