@@ -23,6 +23,25 @@ __device__ __forceinline__ uint32_t residue_code(uint32_t c)
     return ok ? (uint32_t)__popc(kMask & ((1u << (idx & 31u)) - 1u)) : 20u;
 }
 
+/* The key of the window whose 8 residue codes are w.c[]: big-endian base-20
+ * Horner (encoded_kmer, kguts.cc:438-455).  `ok` comes in as what the caller
+ * knows of the window and is cleared by a code-20 residue, which anywhere
+ * kills the window (advance_past_ambig).  The codes travel by value: a
+ * pointer to the caller's array keeps that array in memory until the call is
+ * inlined, and the probes then compile differently. */
+struct WindowCodes {
+    uint32_t c[8];
+};
+__device__ __forceinline__ void window_key(const WindowCodes w, uint64_t &key, bool &ok)
+{
+    const uint32_t *c = w.c;
+    const uint32_t cmax = max(max(max(c[0], c[1]), max(c[2], c[3])), max(max(c[4], c[5]), max(c[6], c[7])));
+    ok = ok && cmax < 20u;
+    const uint32_t ka = ((c[0] * 20 + c[1]) * 20 + c[2]) * 20 + c[3];
+    const uint32_t kb = ((c[4] * 20 + c[5]) * 20 + c[6]) * 20 + c[7];
+    key = (uint64_t)ka * 160000u + kb;
+}
+
 /* NCBI genetic code 11 (trans_table.cc:8-15) indexed e1*16 + e2*4 + e3 with
  * A=0 C=1 G=2 T/U=3 (trans_table.h:45-83); tests/test_fq_host.py re-derives
  * it from the table text */

@@ -168,32 +168,56 @@ hipError_t launch_plan_fused(const uint64_t *seq_off, uint32_t n_seq, uint64_t n
  * num_sigs counts the table's buckets.  0: the reference's slot (key mod
  * num_sigs); shift 2: the line index of kgx_image_set_line_index (4-bucket
  * lines, homes at line starts), with the home mode the index was built with. */
-struct ProbeTable {           /* what a probe reads */
-    const void *buckets;      /* AOS24 or PACKED16 records */
-    uint64_t num_sigs;        /* how many */
-    uint32_t home;            /* the home word of kgx_line_home.h; 0 = the reference's slots */
+/* What a probe reads.  The records' layout and the presence filter describe
+ * that too, so they live here and not in a struct of their own: an image fills
+ * buckets .. layout (kgx_image::probe_table), a context adds the filter when
+ * its option probe_filter is on (ctx_probe_table); the fused kernels read
+ * PACKED16 records without a filter and ignore both. */
+struct ProbeTable {
+    const void *buckets;                /* AOS24 or PACKED16 records */
+    uint64_t num_sigs;                  /* how many */
+    uint32_t home;                      /* the home word of kgx_line_home.h; 0 = the reference's slots */
+    int layout = KGX_LAYOUT_PACKED16;   /* KGX_LAYOUT_* of the records */
+    const uint64_t *filter = nullptr;   /* the presence filter's words, or none */
+    uint32_t filter_log2_words = 0;
     uint64_t magic() const { return mod_magic(num_sigs >> home_shift_of(home)); }
 };
-hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint64_t *seq_off,
-                        const uint64_t *wbase, const uint32_t *tile_seq, uint32_t n_seq,
-                        uint64_t max_tiles, const ProbeTable &t, int layout,
-                        const uint64_t *filter, uint32_t filter_log2_words,
-                        uint4 *hot, uint4 *cold, uint64_t *hit_mask, int probe_j, int variant,
-                        uint32_t lds_kb, uint32_t max_blocks, bool defer, hipStream_t stream,
-                        uint32_t nt_stores = 0);
-/* defer: over an aligned index with marks the line probe runs each slice's
- * first round and then the tile's open chains together, 16 to a load
- * instruction (a context's KGX_PROBE_DEFER); false: rounds per slice.
- * nt_stores 1: the line probe writes its hit records and mask words with
- * non-temporal stores (context option "probe_nt", an A/B knob).
- * max_blocks > 0 caps the line probe's grid (its waves then stride over the
- * tiles; option probe_persist); 0 = one workgroup per 4 tiles.
- * The line probe over fq fragments left as DNA (PACKED16 images, probe_j
- * 1-4): anchor[s] = (first base of fragment s) << 1 | reverse strand; keys as
- * launch_probe over the translated residues (HIT_PACKED16 records) */
-hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64_t *anchor, const uint64_t *wbase,
-                            const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const ProbeTable &t,
-                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks, bool defer,
+struct ProbeBatch {            /* a planned batch (launch_plan) */
+    const uint8_t *bytes;      /* residues; launch_probe_dna: bases */
+    uint64_t n_bytes;
+    /* per sequence: its offset in bytes; launch_probe_dna: anchor[s] = (first
+     * base of fragment s) << 1 | reverse strand */
+    const uint64_t *starts;
+    const uint64_t *wbase;
+    const uint32_t *tile_seq;
+    uint32_t n_seq;
+    uint64_t max_tiles;
+};
+struct ProbeHits {      /* where the hits go (window space, above) */
+    uint4 *hot, *cold;  /* cold: HIT_PLANES only */
+    uint64_t *hit_mask;
+};
+struct ProbeRun { /* how to run */
+    int probe_j;  /* the tile is probe_j * 64 windows */
+    int variant;  /* PROBE_* */
+    uint32_t lds_kb; /* > 0: a line probe workgroup reserves that much LDS (option probe_lds_kb) */
+    /* > 0 caps the line probe's grid (its waves then stride over the tiles;
+     * option probe_persist); 0 = one workgroup per 4 tiles */
+    uint32_t max_blocks;
+    /* over an aligned index with marks the line probe runs each slice's first
+     * round and then the tile's open chains together, 16 to a load instruction
+     * (a context's KGX_PROBE_DEFER); false: rounds per slice */
+    bool defer;
+    /* 1: the line probe writes its hit records and mask words with
+     * non-temporal stores (context option "probe_nt", an A/B knob) */
+    uint32_t nt;
+};
+hipError_t launch_probe(const ProbeBatch &b, const ProbeTable &t, const ProbeHits &h, const ProbeRun &r,
+                        hipStream_t stream);
+/* The line probe over fq fragments left as DNA (PACKED16 images, probe_j
+ * 1-4); keys as launch_probe over the translated residues (HIT_PACKED16
+ * records).  Of `r` it takes probe_j, max_blocks and defer. */
+hipError_t launch_probe_dna(const ProbeBatch &b, const ProbeTable &t, const ProbeHits &h, const ProbeRun &r,
                             hipStream_t stream);
 
 /* ---- kgx_line_index.hip: the resident layouts and the presence filter ---- */

@@ -313,21 +313,6 @@ using namespace kgx;
 /* the line index of an image (kgx.h)                                        */
 /* ------------------------------------------------------------------------ */
 
-/* one of kgx_image_set_line_index's environment switches: "0" clears
- * `value`; "1", unset or empty leaves it at its default (which the twins
- * rule may have cleared); anything else is KGX_EINVAL, with `zero` and `one`
- * naming the two settings */
-static int line_switch(const char *name, const char *zero, const char *one, bool &value)
-{
-    const char *v = getenv(name);
-    if (!v || !*v || !strcmp(v, "1"))
-        return KGX_OK;
-    if (strcmp(v, "0"))
-        return fail(KGX_EINVAL, std::string(name) + ": 0 (" + zero + ") or 1 (" + one + "), not \"" + v + "\"");
-    value = false;
-    return KGX_OK;
-}
-
 int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
 {
     if (!img)
@@ -338,20 +323,20 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
      * (the default), 0 = key mod n_lines (kgx_line_home.h); read at each
      * call, a property of the index it builds */
     bool minimizer = true;
-    if (int rc = line_switch("KGX_LINE_HOME", "mod", "minimizer", minimizer))
+    if (int rc = env_switch("KGX_LINE_HOME", "mod", "minimizer", minimizer))
         return rc;
     const uint32_t home_mode = minimizer ? LINE_HOME_MINIMIZER : LINE_HOME_MOD;
     /* overflow marks on the index's full lines, which end an absent key's
      * chain in one line (kgx_line_home.h): KGX_LINE_MARKS 1 (the default)
      * builds them, 0 builds none; read at each call like KGX_LINE_HOME */
     bool marks = true;
-    if (int rc = line_switch("KGX_LINE_MARKS", "none", "marks", marks))
+    if (int rc = env_switch("KGX_LINE_MARKS", "none", "marks", marks))
         return rc;
     /* twin records, which let two neighbouring windows always share a line
      * (kgx_line_home.h): KGX_LINE_TWINS 1 (the default) builds them where the
      * rule of kgx.h allows, 0 builds none; read at each call like the two above */
     bool twins = minimizer && marks && keys_per_64_lines <= KGX_LINE_TWINS_MAX_LOAD;
-    if (int rc = line_switch("KGX_LINE_TWINS", "none", "twins", twins))
+    if (int rc = env_switch("KGX_LINE_TWINS", "none", "twins", twins))
         return rc;
     /* the service's workgroups hold the probe table's address */
     const auto hold = svc_shutdown_hold(img);

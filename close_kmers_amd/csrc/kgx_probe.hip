@@ -6,10 +6,19 @@
  *            (across sequence boundaries); J probe chains in flight per lane;
  *            hits compacted per tile in window order with wave ballots
  *
+ * In the file's order: the two encodes of a tile (residues, DNA; the key of a
+ * window is window_key, kgx_device.h) and the ordered compaction; probe_kernel,
+ * one lane per chain; probe_line_kernel, one quad or octet per chain and a
+ * table line per load, with the pieces of its aligned body before it -- the
+ * hand-over, the test of one line and the chain rules, each defined once and
+ * used by both of that body's forms; the launchers, which pick the kernel
+ * instance for a batch.
+ *
  * Reference behaviour restated (kguts.cc line numbers): residue map 273-339,
  * window set / rolling code 682-732 and 783-871, probe 585-602.
  */
 #include <algorithm>
+#include <type_traits>
 
 #include "kgx_device.h"
 
@@ -115,13 +124,7 @@ __device__ __forceinline__ void encode_tile(const uint8_t *__restrict__ residues
                        c2 = code_tab[(lo >> 16) & 0xFF], c3 = code_tab[lo >> 24];
         const uint32_t c4 = code_tab[hi & 0xFF], c5 = code_tab[(hi >> 8) & 0xFF],
                        c6 = code_tab[(hi >> 16) & 0xFF], c7 = code_tab[hi >> 24];
-        /* a code-20 residue anywhere kills the window (advance_past_ambig) */
-        const uint32_t cmax = max(max(max(c0, c1), max(c2, c3)), max(max(c4, c5), max(c6, c7)));
-        ok[j] = ok[j] && cmax < 20u;
-        /* big-endian base-20 Horner (encoded_kmer, kguts.cc:438-455) */
-        const uint32_t ka = ((c0 * 20 + c1) * 20 + c2) * 20 + c3;
-        const uint32_t kb = ((c4 * 20 + c5) * 20 + c6) * 20 + c7;
-        key[j] = (uint64_t)ka * 160000u + kb;
+        window_key(WindowCodes{{c0, c1, c2, c3, c4, c5, c6, c7}}, key[j], ok[j]);
         if (a7) { /* the key's two 7-mers, for the home (kgx_line_home.h) */
             const uint32_t cc[8] = {c0, c1, c2, c3, c4, c5, c6, c7};
             seven_mers(cc, a7[j], b7[j]);
@@ -221,11 +224,7 @@ __device__ __forceinline__ void encode_tile_dna(const uint8_t *__restrict__ base
             const uint32_t e = ((e1 << 4) | (e2 << 2) | e3) ^ flip; /* >= 64: a non-base */
             c[i] = cod_tab[min(e, 64u)]; /* unconditional read: entry 64 = 20 */
         }
-        const uint32_t cmax = max(max(max(c[0], c[1]), max(c[2], c[3])), max(max(c[4], c[5]), max(c[6], c[7])));
-        ok[j] = ok[j] && cmax < 20u;
-        const uint32_t ka = ((c[0] * 20 + c[1]) * 20 + c[2]) * 20 + c[3];
-        const uint32_t kb = ((c[4] * 20 + c[5]) * 20 + c[6]) * 20 + c[7];
-        key[j] = (uint64_t)ka * 160000u + kb;
+        window_key(WindowCodes{{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]}}, key[j], ok[j]);
         if (a7)
             seven_mers(c, a7[j], b7[j]);
     }
@@ -404,43 +403,100 @@ __global__ __launch_bounds__(256) void probe_kernel(
  * num_sigs buckets -- same answer, since every bucket has been seen).
  * The matching lane writes the record to LDS for the window's owner.
  *
- * probe_slice_aligned is one 64-window slice of it over an aligned index
- * (line_index_aligned, kgx_line_home.h: whole 4-record lines, line-aligned
- * homes, overflow marks, fewer than 2^32 - 2 lines).  The chain rules are
- * those of the kernel's generic slice; what the alignment settles is left
- * out: a chain's position is a 32-bit line number, every record of a line
- * belongs to the chain and lies inside the table, and a line searched in vain
- * was searched whole, so its overflow mark for the key decides whether the
- * chain goes on.  The owner lane hands its quad three words per instruction: the
- * key's low word, a word with key bits 32-34, the open-chain bit and
- * line_mark of the key, and the home line.  Each lane keeps, per instruction,
- * the key's high bits and the one bit of its own record's last dword that
- * holds the key's mark (or none) in one word: bits 0-2 and 28-31 do not meet.
- * `rec` and `hitf` are the slice's 64 hand-over slots in LDS.
+ * Over an aligned index (line_index_aligned, kgx_line_home.h: whole 4-record
+ * lines, line-aligned homes, overflow marks, fewer than 2^32 - 2 lines) the
+ * chain rules are those of the kernel's generic slice; what the alignment
+ * settles is left out: a chain's position is a 32-bit line number, every
+ * record of a line belongs to the chain and lies inside the table, and a line
+ * searched in vain was searched whole, so its overflow mark for the key
+ * decides whether the chain goes on.  Both forms of the aligned body -- rounds
+ * per slice (probe_slice_aligned) and deferred (probe_slice_round0, then
+ * probe_tile_deferred) -- are made of the pieces that follow, each rule
+ * defined once.
  */
-__device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ packed, uint32_t n_lines, uint64_t key,
-                                                    bool ok, uint32_t home_line, uint32_t q, uint32_t c, uint4 *rec,
-                                                    uint8_t *hitf)
+constexpr uint32_t LINE_G = 4, LINE_NQ = 64 / LINE_G; /* the index's records per line; windows per instruction */
+constexpr uint32_t MARKED = 1u << LINE_G;             /* in a line's word: the line carries the key's mark */
+constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+static_assert(KEY_HI == 7u && (MARK_BITS_W & KEY_HI) == 0, "key bits 32-34 beside the mark bit");
+
+/* what a window's owner hands its quad beside the key's low word and the home
+ * line: key bits 32-34, the open-chain bit, line_mark of the key from bit 4 */
+__device__ __forceinline__ uint32_t owner_word(uint64_t key, bool ok)
 {
-    constexpr uint32_t G = 4, NQ = 64 / G;
-    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
-    constexpr uint32_t MAX_HI = (uint32_t)(MAX_ENCODED >> 32), MAX_LO = (uint32_t)MAX_ENCODED;
-    static_assert(KEY_HI == 7u && (MARK_BITS_W & KEY_HI) == 0, "key bits 32-34 beside the mark bit");
-    const uint32_t own = (uint32_t)(key >> 32) | (uint32_t)ok << 3 | line_mark(key) << 4;
-    uint32_t klo[G], kw[G], ln[G];
-    uint32_t live = 0; /* bit i: instruction i's chain is still open */
+    return (uint32_t)(key >> 32) | (uint32_t)ok << 3 | line_mark(key) << 4;
+}
+/* what lane c of the quad keeps of an owner's word: the key's high bits and
+ * the one bit of its own record's last dword that holds the key's mark (or
+ * none) in one word: bits 0-2 and 28-31 do not meet */
+__device__ __forceinline__ uint32_t lane_key_word(uint32_t own, uint32_t c)
+{
+    const uint32_t g = own >> 4;
+    return (own & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+}
+/* The hand-over: lane c of quad q takes the quad's G chains of a slice from
+ * their owners, lane NQ i + q for instruction i.  Returns the open chains,
+ * bit i for instruction i. */
+__device__ __forceinline__ uint32_t quad_hand_over(uint64_t key, uint32_t own, uint32_t home_line, uint32_t q, uint32_t c,
+                                                   uint32_t (&klo)[LINE_G], uint32_t (&kw)[LINE_G],
+                                                   uint32_t (&ln)[LINE_G])
+{
+    uint32_t live = 0;
 #pragma unroll
-    for (int i = 0; i < (int)G; i++) {
-        const int owner = (int)(NQ * i + q);
+    for (int i = 0; i < (int)LINE_G; i++) {
+        const int owner = (int)(LINE_NQ * i + q);
         klo[i] = (uint32_t)__shfl((int)(uint32_t)key, owner);
         ln[i] = (uint32_t)__shfl((int)home_line, owner);
         const uint32_t o = (uint32_t)__shfl((int)own, owner);
         live |= (o >> 3 & 1u) << i;
-        const uint32_t g = o >> 4;
-        kw[i] = (o & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+        kw[i] = lane_key_word(o, c);
     }
-    const uint32_t cbit = 1u << c, upto = (2u << c) - 1u; /* this lane's record of its line; it and those before */
-    constexpr uint32_t MARKED = 1u << G;
+    return live;
+}
+
+/* The test of one line, d = this lane's record of it (cbit = 1 << c): the
+ * line's word, ORed over the quad by two DPP moves (a quad is the lanes of one
+ * line, and every lane of the wave is active here) -- bit c, record c holds
+ * the key or is empty; MARKED, the line carries the key's mark; 0 for a closed
+ * chain -- and `diff`, 0 where this lane's record holds the key.
+ * The record's key is tested in its two words, and for equality through xor:
+ * after `d.x == klo` the compiler hands over klo in d.x's place, and after a
+ * 64-bit compare it builds a register pair in the loaded one's; either way the
+ * record is put together again by copies that wait for the load at the branch
+ * join.  `> MAX_ENCODED` is two 32-bit tests for the same reason. */
+__device__ __forceinline__ uint32_t quad_line_word(const uint4 &d, uint32_t klo, uint32_t kw, bool open,
+                                                   uint32_t cbit, uint32_t &diff)
+{
+    constexpr uint32_t MAX_HI = (uint32_t)(MAX_ENCODED >> 32), MAX_LO = (uint32_t)MAX_ENCODED;
+    const uint32_t kh = d.y & KEY_HI;
+    diff = (d.x ^ klo) | ((d.y ^ kw) & KEY_HI);
+    const bool ends = diff == 0 || kh > MAX_HI || (kh == MAX_HI && d.x > MAX_LO);
+    uint32_t w = (ends ? cbit : 0u) | ((d.w & kw) >= 1u << 28 ? MARKED : 0u);
+    w = open ? w : 0u;
+    w |= (uint32_t)xor_lane((int32_t)w, 1);
+    w |= (uint32_t)xor_lane((int32_t)w, 2);
+    return w;
+}
+/* the line's first match or empty bucket ends the chain; a match there is the
+ * hit: this lane's record (diff 0), none of the line's word set before it
+ * (cbit = 1 << c, this lane's record; upto = (2 << c) - 1, it and those before) */
+__device__ __forceinline__ bool lane_hits(uint32_t diff, uint32_t w, uint32_t cbit, uint32_t upto)
+{
+    return diff == 0 && (w & upto) == cbit;
+}
+/* on: nothing found, and the key's mark set (a full line whose mark for the
+ * key is clear was never passed by it) */
+__device__ __forceinline__ bool chain_goes_on(uint32_t w) { return (w & (2u * MARKED - 1)) == MARKED; }
+__device__ __forceinline__ uint32_t next_line(uint32_t ln, uint32_t n_lines) { return ln + 1 == n_lines ? 0 : ln + 1; }
+
+/* a 64-window slice to its end; `rec` and `hitf` are its 64 hand-over slots in LDS */
+__device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ packed, uint32_t n_lines, uint64_t key,
+                                                    bool ok, uint32_t home_line, uint32_t q, uint32_t c, uint4 *rec,
+                                                    uint8_t *hitf)
+{
+    constexpr uint32_t G = LINE_G, NQ = LINE_NQ;
+    uint32_t klo[G], kw[G], ln[G];
+    uint32_t live = quad_hand_over(key, owner_word(key, ok), home_line, q, c, klo, kw, ln); /* bit i: chain i is open */
+    const uint32_t cbit = 1u << c, upto = (2u << c) - 1u;
     const uint32_t max_lines = n_lines + 2; /* lines a chain may visit before it has covered the table */
     for (uint32_t round = 0;; round++) {
         /* only open chains load; d is fresh each round (no merge with an
@@ -453,29 +509,11 @@ __device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ pa
         uint32_t hitm = 0; /* bit i: this lane's record is instruction i's hit */
 #pragma unroll
         for (int i = 0; i < (int)G; i++) {
-            /* The record's key is tested in its two words, and for equality
-             * through xor: after `d.x == klo` the compiler hands over klo in
-             * d.x's place, and after a 64-bit compare it builds a register
-             * pair in the loaded one's; either way the record is put together
-             * again by copies that wait for the load at the branch join. */
-            const uint32_t kh = d[i].y & KEY_HI;
-            const uint32_t diff = (d[i].x ^ klo[i]) | ((d[i].y ^ kw[i]) & KEY_HI); /* 0: the key */
-            const bool ends = diff == 0 || kh > MAX_HI || (kh == MAX_HI && d[i].x > MAX_LO); /* or > MAX_ENCODED */
-            /* the line's word, ORed over the quad by two DPP moves (a quad
-             * is the lanes of one line, and every lane of the wave is active
-             * here): bit c, record c holds the key or is empty; MARKED, the
-             * line carries the key's mark.  0 for a closed chain. */
-            uint32_t w = (ends ? cbit : 0u) | ((d[i].w & kw[i]) >= 1u << 28 ? MARKED : 0u);
-            w = live >> i & 1u ? w : 0u;
-            w |= (uint32_t)xor_lane((int32_t)w, 1);
-            w |= (uint32_t)xor_lane((int32_t)w, 2);
-            /* the line's first match or empty bucket ends the chain; a match
-             * there is the hit */
-            hitm |= diff == 0 && (w & upto) == cbit ? 1u << i : 0u;
-            /* on: nothing found, and the key's mark set (a full line whose
-             * mark for the key is clear was never passed by it) */
-            live = (w & (2u * MARKED - 1)) == MARKED ? live : live & ~(1u << i);
-            ln[i] = ln[i] + 1 == n_lines ? 0 : ln[i] + 1;
+            uint32_t diff;
+            const uint32_t w = quad_line_word(d[i], klo[i], kw[i], live >> i & 1u, cbit, diff);
+            hitm |= lane_hits(diff, w, cbit, upto) ? 1u << i : 0u;
+            live = chain_goes_on(w) ? live : live & ~(1u << i);
+            ln[i] = next_line(ln[i], n_lines);
         }
         /* the hits are handed to the windows' owners after all four tests:
          * no branch stands between the tests, so their instructions mix */
@@ -498,48 +536,19 @@ __device__ __forceinline__ void probe_slice_aligned(const uint4 *__restrict__ pa
  * walked slice by slice, a few lanes at a time at the whole round's cost, but
  * once for the tile, packed 16 to a load instruction.
  *
- * quad_line_word is probe_slice_aligned's test of one line: the quad's word
- * (bit c: record c holds the key or is empty; bit G: the line carries the
- * key's mark; 0 for a closed chain) and `diff`, 0 where this lane's record
- * holds the key.
+ * Round 0 of a 64-window slice, straight-line: the hand-over and one round
+ * without the loop -- the round of probe_slice_aligned, written out again
+ * because a function shared by the two changes what the compiler makes of
+ * both.  Returns the quad's open chains, bit i for instruction i (the same in
+ * the quad's four lanes); their next line is the one after the home.
  */
-__device__ __forceinline__ uint32_t quad_line_word(const uint4 &d, uint32_t klo, uint32_t kw, bool open,
-                                                   uint32_t cbit, uint32_t &diff)
-{
-    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32), MARKED = 1u << 4;
-    constexpr uint32_t MAX_HI = (uint32_t)(MAX_ENCODED >> 32), MAX_LO = (uint32_t)MAX_ENCODED;
-    const uint32_t kh = d.y & KEY_HI;
-    diff = (d.x ^ klo) | ((d.y ^ kw) & KEY_HI);
-    const bool ends = diff == 0 || kh > MAX_HI || (kh == MAX_HI && d.x > MAX_LO);
-    uint32_t w = (ends ? cbit : 0u) | ((d.w & kw) >= 1u << 28 ? MARKED : 0u);
-    w = open ? w : 0u;
-    w |= (uint32_t)xor_lane((int32_t)w, 1);
-    w |= (uint32_t)xor_lane((int32_t)w, 2);
-    return w;
-}
-
-/* Round 0 of a 64-window slice, straight-line: probe_slice_aligned's hand-over
- * and one round of it without the loop.  Returns the quad's open chains, bit i
- * for instruction i (the same in the quad's four lanes); their next line is
- * the one after the home. */
 __device__ __forceinline__ uint32_t probe_slice_round0(const uint4 *__restrict__ packed, uint64_t key, uint32_t own,
                                                        uint32_t home_line, uint32_t q, uint32_t c, uint4 *rec,
                                                        uint8_t *hitf)
 {
-    constexpr uint32_t G = 4, NQ = 64 / G, MARKED = 1u << G;
-    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+    constexpr uint32_t G = LINE_G, NQ = LINE_NQ;
     uint32_t klo[G], kw[G], ln[G];
-    uint32_t live = 0;
-#pragma unroll
-    for (int i = 0; i < (int)G; i++) {
-        const int owner = (int)(NQ * i + q);
-        klo[i] = (uint32_t)__shfl((int)(uint32_t)key, owner);
-        ln[i] = (uint32_t)__shfl((int)home_line, owner);
-        const uint32_t o = (uint32_t)__shfl((int)own, owner);
-        live |= (o >> 3 & 1u) << i;
-        const uint32_t g = o >> 4;
-        kw[i] = (o & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
-    }
+    uint32_t live = quad_hand_over(key, own, home_line, q, c, klo, kw, ln);
     const uint32_t cbit = 1u << c, upto = (2u << c) - 1u;
     uint4 d[G];
 #pragma unroll
@@ -551,8 +560,8 @@ __device__ __forceinline__ uint32_t probe_slice_round0(const uint4 *__restrict__
     for (int i = 0; i < (int)G; i++) {
         uint32_t diff;
         const uint32_t w = quad_line_word(d[i], klo[i], kw[i], live >> i & 1u, cbit, diff);
-        hitm |= diff == 0 && (w & upto) == cbit ? 1u << i : 0u;
-        live = (w & (2u * MARKED - 1)) == MARKED ? live : live & ~(1u << i);
+        hitm |= lane_hits(diff, w, cbit, upto) ? 1u << i : 0u;
+        live = chain_goes_on(w) ? live : live & ~(1u << i);
     }
 #pragma unroll
     for (int i = 0; i < (int)G; i++)
@@ -565,8 +574,8 @@ __device__ __forceinline__ uint32_t probe_slice_round0(const uint4 *__restrict__
 
 /* The tile's n_open chains left open by round 0, in window order in `list`
  * (window slots of the tile); chain w's entry lies in rec[w], which is free
- * until the chain hits: key low word, the owner's word of probe_slice_aligned
- * (key bits 32-34, line_mark from bit 4), next line.  Quad q walks entry
+ * until the chain hits: key low word, owner_word (its key bits 32-34 and
+ * line_mark are used), next line.  Quad q walks entry
  * 16 p + q of pass p, all 16 in one load instruction per round, by
  * probe_slice_aligned's rules; a chain has visited one line already, so the
  * rounds count from 1 towards the n_lines + 2 that cover the table. */
@@ -574,8 +583,7 @@ __device__ __forceinline__ void probe_tile_deferred(const uint4 *__restrict__ pa
                                                     uint32_t n_open, const uint8_t *list, uint32_t q, uint32_t c,
                                                     uint4 *rec, uint8_t *hitf)
 {
-    constexpr uint32_t G = 4, NQ = 64 / G, MARKED = 1u << G;
-    constexpr uint32_t KEY_HI = (uint32_t)(PACK_KEY_MASK >> 32);
+    constexpr uint32_t G = LINE_G, NQ = LINE_NQ;
     const uint32_t cbit = 1u << c, upto = (2u << c) - 1u;
     const uint32_t max_lines = n_lines + 2;
     for (uint32_t p = 0; p < n_open; p += NQ) {
@@ -586,8 +594,7 @@ __device__ __forceinline__ void probe_tile_deferred(const uint4 *__restrict__ pa
             w = list[p + q];
             e = rec[w];
         }
-        const uint32_t klo = e.x, g = e.y >> 4;
-        const uint32_t kw = (e.y & KEY_HI) | (c == mark_record(g) ? 1u << mark_bit_w(g) : 0u);
+        const uint32_t klo = e.x, kw = lane_key_word(e.y, c);
         uint32_t ln = e.z;
         for (uint32_t round = 1;; round++) {
             uint4 d; /* fresh each round, as in probe_slice_aligned */
@@ -595,17 +602,25 @@ __device__ __forceinline__ void probe_tile_deferred(const uint4 *__restrict__ pa
                 d = packed[(uint64_t)ln * G + c];
             uint32_t diff;
             const uint32_t lw = quad_line_word(d, klo, kw, live, cbit, diff);
-            if (diff == 0 && (lw & upto) == cbit) {
+            if (lane_hits(diff, lw, cbit, upto)) {
                 rec[w] = d;
                 hitf[w] = 1;
             }
-            live = live && (lw & (2u * MARKED - 1)) == MARKED && round + 1 < max_lines;
-            ln = ln + 1 == n_lines ? 0 : ln + 1;
+            const bool on = chain_goes_on(lw);
+            live = live && on && round + 1 < max_lines;
+            ln = next_line(ln, n_lines);
             if (!__any(live))
                 break;
         }
     }
 }
+
+/* The static LDS of a line probe workgroup at the default J = 2, which is what
+ * launch_probe takes off a probe_lds_kb reservation: a 128-window tile's
+ * 8960 B (the code table's 256, 4 waves x 128 windows of 16-B hand-over
+ * records and of hit flags) counted as 9 KB, and with the deferred form's list
+ * of open chains, 4 x 128 B more. */
+constexpr uint32_t PROBE_LINE_LDS = 9216, PROBE_LINE_LDS_DEFER = PROBE_LINE_LDS + 512;
 
 template <int J, int G, bool DNA, bool MARKS, bool TWINS, bool DEFER>
 __global__ __launch_bounds__(256) void probe_line_kernel(
@@ -622,6 +637,9 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
     __shared__ uint8_t lds_hit[PROBE_WAVES][T];
     __shared__ uint8_t lds_open[PROBE_WAVES][DEFER ? T : 1]; /* DEFER: the tile's open chains (window slots) */
     static_assert(T <= 256, "a window slot is a byte of lds_open");
+    static_assert(J != 2 || sizeof(code_tab) + sizeof(cod_tab) + sizeof(lds_rec) + sizeof(lds_hit) + sizeof(lds_open) <=
+                                (DEFER ? PROBE_LINE_LDS_DEFER : PROBE_LINE_LDS),
+                  "the launcher's count of this LDS");
     if (DNA) {
         const uint32_t b = threadIdx.x | 0x20u; /* ACGTU either case (trans_table.h:45-68) */
         const bool base = b == 'a' || b == 'c' || b == 'g' || b == 't' || b == 'u';
@@ -641,181 +659,181 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
      * next tile lies past the batch's last window */
     for (uint64_t tile = (uint64_t)blockIdx.x * PROBE_WAVES + wave; tile * T < W;
          tile += (uint64_t)gridDim.x * PROBE_WAVES) {
-    const uint64_t g0 = tile * T;
+        const uint64_t g0 = tile * T;
 
-    uint64_t key[J];
-    uint32_t pos[J], sq[J];
-    bool ok[J];
-    const uint32_t q = lane / G, c = lane % G;
-    /* MARKS: the table is an aligned index (the launcher: line_index_aligned,
-     * G = 4).  Its homes come from the 7-mers the encode holds and its slices
-     * run probe_slice_aligned; without, the kernel is the generic one below
-     * and holds none of the aligned body's instructions or registers */
-    /* TWINS: the index holds every key under the homes of both its 7-mers
-     * (kgx_line_home.h), and a window starts at pair_home of its index in the
-     * batch: g0, 64 j and the 16 windows of an instruction are all even, so
-     * windows g (even) and g + 1 are neighbouring quads of one instruction
-     * and, in one sequence, ask for one line */
-    static_assert(!MARKS || G == 4, "the index's lines are 4 records");
-    static_assert(!TWINS || MARKS, "twin records come with marks only");
-    if constexpr (MARKS) {
-        uint32_t a7[J], b7[J];
-        if (DNA)
-            encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab,
-                               cod_tab, key, ok, pos, sq, a7, b7);
-        else
-            encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
-                           pos, sq, a7, b7);
-        const uint32_t n_lines = (uint32_t)(num_sigs / G);
-        uint32_t home_line[J];
-#pragma unroll
-        for (int j = 0; j < J; j++) {
-            if (TWINS)
-                home_line[j] = ok[j] ? (uint32_t)pair_home(a7[j], b7[j], lane, n_lines, magic) : 0; /* g's parity is the lane's */
+        uint64_t key[J];
+        uint32_t pos[J], sq[J];
+        bool ok[J];
+        const uint32_t q = lane / G, c = lane % G;
+        /* MARKS: the table is an aligned index (the launcher: line_index_aligned,
+         * G = 4).  Its homes come from the 7-mers the encode holds and its slices
+         * run probe_slice_aligned; without, the kernel is the generic one below
+         * and holds none of the aligned body's instructions or registers */
+        /* TWINS: the index holds every key under the homes of both its 7-mers
+         * (kgx_line_home.h), and a window starts at pair_home of its index in the
+         * batch: g0, 64 j and the 16 windows of an instruction are all even, so
+         * windows g (even) and g + 1 are neighbouring quads of one instruction
+         * and, in one sequence, ask for one line */
+        static_assert(!MARKS || G == 4, "the index's lines are 4 records");
+        static_assert(!TWINS || MARKS, "twin records come with marks only");
+        if constexpr (MARKS) {
+            uint32_t a7[J], b7[J];
+            if (DNA)
+                encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab,
+                                   cod_tab, key, ok, pos, sq, a7, b7);
             else
-                home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(home)) : 0;
-            lds_hit[wave][64 * j + lane] = 0;
-        }
-        if constexpr (DEFER) {
-            /* each slice's first round, then the tile's open chains together.
-             * A window's owner learns from its quad (lanes 4 (l % 16) on,
-             * instruction l / 16) whether the chain is open and files it: the
-             * ballot is in window order, so under TWINS an even window and
-             * its successor are neighbouring quads of a deferred instruction
-             * too (unless a pass boundary parts them) and ask for one line */
-            uint32_t n_open = 0; /* per tile: a wave may walk many */
+                encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
+                               pos, sq, a7, b7);
+            const uint32_t n_lines = (uint32_t)(num_sigs / G);
+            uint32_t home_line[J];
 #pragma unroll
             for (int j = 0; j < J; j++) {
-                const uint32_t own = (uint32_t)(key[j] >> 32) | (uint32_t)ok[j] << 3 | line_mark(key[j]) << 4;
-                const uint32_t live = probe_slice_round0(packed, key[j], own, home_line[j], q, c,
-                                                         &lds_rec[wave][64 * j], &lds_hit[wave][64 * j]);
-                const uint32_t of_quad = (uint32_t)__shfl((int)live, (int)(G * (lane % NQ)));
-                const bool open = of_quad >> (lane / NQ) & 1u;
-                const uint64_t m = __ballot(open);
-                if (open) {
-                    const uint32_t next = home_line[j] + 1 == n_lines ? 0 : home_line[j] + 1;
-                    lds_rec[wave][64 * j + lane] = make_uint4((uint32_t)key[j], own, next, 0);
-                    lds_open[wave][n_open + lanes_below(m)] = (uint8_t)(64 * j + lane);
-                }
-                n_open += (uint32_t)__popcll(m);
+                if (TWINS)
+                    home_line[j] = ok[j] ? (uint32_t)pair_home(a7[j], b7[j], lane, n_lines, magic) : 0; /* g's parity is the lane's */
+                else
+                    home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(home)) : 0;
+                lds_hit[wave][64 * j + lane] = 0;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            probe_tile_deferred(packed, n_lines, n_open, lds_open[wave], q, c, lds_rec[wave], lds_hit[wave]);
-        } else {
-        /* one 64-window slice at a time, as below */
+            if constexpr (DEFER) {
+                /* each slice's first round, then the tile's open chains together.
+                 * A window's owner learns from its quad (lanes 4 (l % 16) on,
+                 * instruction l / 16) whether the chain is open and files it: the
+                 * ballot is in window order, so under TWINS an even window and
+                 * its successor are neighbouring quads of a deferred instruction
+                 * too (unless a pass boundary parts them) and ask for one line */
+                uint32_t n_open = 0; /* per tile: a wave may walk many */
 #pragma unroll
-        for (int j = 0; j < J; j++)
-            probe_slice_aligned(packed, n_lines, key[j], ok[j], home_line[j], q, c, &lds_rec[wave][64 * j],
-                                &lds_hit[wave][64 * j]);
-        }
-    } else {
-    if (DNA)
-        encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, cod_tab,
-                           key, ok, pos, sq);
-    else
-        encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
-                       pos, sq);
-    uint64_t first[J]; /* the chain's first bucket */
-#pragma unroll
-    for (int j = 0; j < J; j++) {
-        first[j] = ok[j] ? home_bucket(key[j], num_sigs, magic, home) : 0; /* line starts with the index */
-        lds_hit[wave][64 * j + lane] = 0;
-    }
-
-    /* lines a chain may visit before it has covered the whole table */
-    const uint64_t max_lines = num_sigs / G + 2;
-    /* One 64-window slice (G instructions) at a time, each with its own
-     * rounds: the wave holds G lines in flight instead of J * G, so a tile of
-     * any J needs the registers of J = 1 (8 waves per SIMD at G = 4, where
-     * all of a 128-window tile's chains at once left 5).  With the minimizer
-     * home nearly every wave runs a second, almost empty round, and it is
-     * the other resident waves that cover it. */
-#pragma unroll
-    for (int j = 0; j < J; j++) {
-    uint64_t K[G], cur[G];
-    /* bit i: instruction i's chain is still open */
-    uint32_t live = 0;
-    const uint32_t own = (uint32_t)ok[j];
-#pragma unroll
-    for (int i = 0; i < G; i++) {
-        const uint32_t owner = NQ * i + q;
-        K[i] = __shfl(key[j], (int)owner);
-        cur[i] = __shfl(first[j], (int)owner);
-        const uint32_t o = (uint32_t)__shfl((int)own, (int)owner);
-        live |= (o & 1u) << i;
-    }
-    for (uint64_t round = 0;; round++) {
-        /* only open chains load; d is fresh each round (no merge with an
-         * older value at the branch join, so no wait for the load there) */
-        uint4 d[G];
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            const uint64_t line = cur[i] - cur[i] % G;
-            if ((live >> i & 1u) && line + c < num_sigs)
-                d[i] = packed[line + c];
-        }
-        bool more = false;
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            const bool act = live >> i & 1u;
-            const uint64_t line = cur[i] - cur[i] % G;
-            const uint64_t b = line + c;
-            const uint64_t kb = ((uint64_t)d[i].y << 32 | d[i].x) & PACK_KEY_MASK;
-            const bool valid = act && b < num_sigs && b >= cur[i];
-            const uint64_t mm = __ballot(valid && kb == K[i]);
-            const uint64_t me = __ballot(valid && kb > MAX_ENCODED);
-            const uint32_t gm = (uint32_t)(mm >> (G * q)) & ((1u << G) - 1);
-            const uint32_t ge = (uint32_t)(me >> (G * q)) & ((1u << G) - 1);
-            if (act) {
-                const uint32_t ev = gm | ge;
-                if (ev) {
-                    const uint32_t first = __builtin_ctz(ev);
-                    if (c == first && (gm >> first & 1u)) {
-                        const uint32_t w = 64 * j + NQ * i + q;
-                        lds_rec[wave][w] = d[i];
-                        lds_hit[wave][w] = 1;
+                for (int j = 0; j < J; j++) {
+                    const uint32_t own = owner_word(key[j], ok[j]);
+                    const uint32_t live = probe_slice_round0(packed, key[j], own, home_line[j], q, c,
+                                                             &lds_rec[wave][64 * j], &lds_hit[wave][64 * j]);
+                    const uint32_t of_quad = (uint32_t)__shfl((int)live, (int)(G * (lane % NQ)));
+                    const bool open = of_quad >> (lane / NQ) & 1u;
+                    const uint64_t m = __ballot(open);
+                    if (open) {
+                        lds_rec[wave][64 * j + lane] = make_uint4((uint32_t)key[j], own, next_line(home_line[j], n_lines), 0);
+                        lds_open[wave][n_open + lanes_below(m)] = (uint8_t)(64 * j + lane);
                     }
-                    live &= ~(1u << i);
-                } else if (round + 1 >= max_lines) {
-                    live &= ~(1u << i);
-                } else {
-                    cur[i] = line + G >= num_sigs ? 0 : line + G;
-                    more = true;
+                    n_open += (uint32_t)__popcll(m);
+                }
+                wave_lds_sync();
+                probe_tile_deferred(packed, n_lines, n_open, lds_open[wave], q, c, lds_rec[wave], lds_hit[wave]);
+            } else {
+                /* one 64-window slice at a time, as below */
+#pragma unroll
+                for (int j = 0; j < J; j++)
+                    probe_slice_aligned(packed, n_lines, key[j], ok[j], home_line[j], q, c, &lds_rec[wave][64 * j],
+                                        &lds_hit[wave][64 * j]);
+            }
+        } else {
+            if (DNA)
+                encode_tile_dna<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, cod_tab,
+                                   key, ok, pos, sq);
+            else
+                encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
+                               pos, sq);
+            uint64_t first[J]; /* the chain's first bucket */
+#pragma unroll
+            for (int j = 0; j < J; j++) {
+                first[j] = ok[j] ? home_bucket(key[j], num_sigs, magic, home) : 0; /* line starts with the index */
+                lds_hit[wave][64 * j + lane] = 0;
+            }
+
+            /* lines a chain may visit before it has covered the whole table */
+            const uint64_t max_lines = num_sigs / G + 2;
+            /* One 64-window slice (G instructions) at a time, each with its own
+             * rounds: the wave holds G lines in flight instead of J * G, so a tile of
+             * any J needs the registers of J = 1 (8 waves per SIMD at G = 4, where
+             * all of a 128-window tile's chains at once left 5).  With the minimizer
+             * home nearly every wave runs a second, almost empty round, and it is
+             * the other resident waves that cover it. */
+#pragma unroll
+            for (int j = 0; j < J; j++) {
+                uint64_t K[G], cur[G];
+                /* bit i: instruction i's chain is still open */
+                uint32_t live = 0;
+                const uint32_t own = (uint32_t)ok[j];
+#pragma unroll
+                for (int i = 0; i < G; i++) {
+                    const uint32_t owner = NQ * i + q;
+                    K[i] = __shfl(key[j], (int)owner);
+                    cur[i] = __shfl(first[j], (int)owner);
+                    const uint32_t o = (uint32_t)__shfl((int)own, (int)owner);
+                    live |= (o & 1u) << i;
+                }
+                for (uint64_t round = 0;; round++) {
+                    /* only open chains load; d is fresh each round (no merge with an
+                     * older value at the branch join, so no wait for the load there) */
+                    uint4 d[G];
+#pragma unroll
+                    for (int i = 0; i < G; i++) {
+                        const uint64_t line = cur[i] - cur[i] % G;
+                        if ((live >> i & 1u) && line + c < num_sigs)
+                            d[i] = packed[line + c];
+                    }
+                    bool more = false;
+#pragma unroll
+                    for (int i = 0; i < G; i++) {
+                        const bool act = live >> i & 1u;
+                        const uint64_t line = cur[i] - cur[i] % G;
+                        const uint64_t b = line + c;
+                        const uint64_t kb = ((uint64_t)d[i].y << 32 | d[i].x) & PACK_KEY_MASK;
+                        const bool valid = act && b < num_sigs && b >= cur[i];
+                        const uint64_t mm = __ballot(valid && kb == K[i]);
+                        const uint64_t me = __ballot(valid && kb > MAX_ENCODED);
+                        const uint32_t gm = (uint32_t)(mm >> (G * q)) & ((1u << G) - 1);
+                        const uint32_t ge = (uint32_t)(me >> (G * q)) & ((1u << G) - 1);
+                        if (act) {
+                            const uint32_t ev = gm | ge;
+                            if (ev) {
+                                const uint32_t first = __builtin_ctz(ev);
+                                if (c == first && (gm >> first & 1u)) {
+                                    const uint32_t w = 64 * j + NQ * i + q;
+                                    lds_rec[wave][w] = d[i];
+                                    lds_hit[wave][w] = 1;
+                                }
+                                live &= ~(1u << i);
+                            } else if (round + 1 >= max_lines) {
+                                live &= ~(1u << i);
+                            } else {
+                                cur[i] = line + G >= num_sigs ? 0 : line + G;
+                                more = true;
+                            }
+                        }
+                    }
+                    if (!__any(more))
+                        break;
                 }
             }
         }
-        if (!__any(more))
-            break;
-    }
-    } /* slices */
-    } /* generic */
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 
-    bool hit[J];
-    uint4 pv[J];
+        bool hit[J];
+        uint4 pv[J];
 #pragma unroll
-    for (int j = 0; j < J; j++) {
-        hit[j] = lds_hit[wave][64 * j + lane] != 0;
-        pv[j] = hit[j] ? lds_rec[wave][64 * j + lane] : make_uint4(0, 0, 0, 0);
+        for (int j = 0; j < J; j++) {
+            hit[j] = lds_hit[wave][64 * j + lane] != 0;
+            pv[j] = hit[j] ? lds_rec[wave][64 * j + lane] : make_uint4(0, 0, 0, 0);
+        }
+        store_tile_hits<J, true>(hit, key, pv, pos, sq, g0, W, lane, hot, cold, hit_mask, nt != 0);
     }
-    store_tile_hits<J, true>(hit, key, pv, pos, sq, g0, W, lane, hot, cold, hit_mask, nt != 0);
-    } /* tiles */
 }
 
-template <int J, int G, bool DNA = false>
-static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *residues, uint64_t n_residues,
-                              const uint64_t *seq_off, const uint64_t *wbase, const uint32_t *tile_seq,
-                              uint32_t n_seq, const ProbeTable &t, uint4 *hot, uint4 *cold, uint64_t *hit_mask,
-                              uint32_t dyn_lds, bool defer, uint32_t nt = 0)
+/* f(std::integral_constant<int, V>{}) for the V of Vs... that v equals; false,
+ * and no call, when it equals none */
+template <int... Vs, class F> static bool with_constant(int v, F &&f)
 {
-    /* the aligned slice body, with the mark test, only over an aligned index
-     * (kgx_line_home.h); every other table runs the generic kernel, which
-     * ignores marks and stays exact.  `defer` picks the aligned body's form,
-     * both compiled: no uniform branch stands in a round */
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+template <int J, int G, bool DNA>
+static void launch_probe_line(dim3 grid, uint32_t dyn_lds, const ProbeBatch &b, const ProbeTable &t, uint4 *hot,
+                              uint4 *cold, uint64_t *hit_mask, bool defer, uint32_t nt, hipStream_t stream)
+{
+    /* the aligned forms, with the mark test, only over an aligned index
+     * (kgx_line_home.h); every other table runs the generic tile, which
+     * ignores marks and stays exact.  `defer` picks the aligned form, both
+     * compiled: no uniform branch stands in a round */
     auto *kernel = probe_line_kernel<J, G, DNA, false, false, false>;
     if constexpr (G == 4)
         if (line_index_aligned(t.num_sigs, t.home)) {
@@ -826,127 +844,78 @@ static void launch_probe_line(dim3 grid, hipStream_t stream, const uint8_t *resi
                 kernel = home_twins_of(t.home) ? probe_line_kernel<J, G, DNA, true, true, false>
                                                : probe_line_kernel<J, G, DNA, true, false, false>;
         }
-    hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, residues, n_residues, seq_off, wbase,
-                       tile_seq, n_seq, static_cast<const uint4 *>(t.buckets), t.num_sigs, t.magic(), t.home, hot,
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), dyn_lds, stream, b.bytes, b.n_bytes, b.starts, b.wbase,
+                       b.tile_seq, b.n_seq, static_cast<const uint4 *>(t.buckets), t.num_sigs, t.magic(), t.home, hot,
                        cold, hit_mask, nt);
 }
 
 template <int J, int MODE>
-static void launch_probe_m(dim3 grid, hipStream_t stream, const uint8_t *residues, uint64_t n_residues,
-                           const uint64_t *seq_off, const uint64_t *wbase, const uint32_t *tile_seq,
-                           uint32_t n_seq, const ProbeTable &t, const uint64_t *filter, uint32_t filter_log2,
-                           uint4 *hot, uint4 *cold, uint64_t *hit_mask)
+static void launch_probe_bucket(dim3 grid, const ProbeBatch &b, const ProbeTable &t, const ProbeHits &h,
+                                hipStream_t stream)
 {
-    if (filter)
-        hipLaunchKernelGGL((probe_kernel<J, MODE, true>), grid, dim3(64 * PROBE_WAVES), 0, stream, residues,
-                           n_residues, seq_off, wbase, tile_seq, n_seq, t.buckets, t.num_sigs, t.magic(), t.home,
-                           filter, filter_log2, hot, cold, hit_mask);
-    else
-        hipLaunchKernelGGL((probe_kernel<J, MODE, false>), grid, dim3(64 * PROBE_WAVES), 0, stream, residues,
-                           n_residues, seq_off, wbase, tile_seq, n_seq, t.buckets, t.num_sigs, t.magic(), t.home,
-                           filter, filter_log2, hot, cold, hit_mask);
+    auto *kernel = t.filter ? probe_kernel<J, MODE, true> : probe_kernel<J, MODE, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * PROBE_WAVES), 0, stream, b.bytes, b.n_bytes, b.starts, b.wbase,
+                       b.tile_seq, b.n_seq, t.buckets, t.num_sigs, t.magic(), t.home, t.filter, t.filter_log2_words,
+                       h.hot, h.cold, h.hit_mask);
 }
 
-template <int J>
-static void launch_probe_j(dim3 grid, hipStream_t stream, int mode, const uint8_t *residues,
-                           uint64_t n_residues, const uint64_t *seq_off, const uint64_t *wbase,
-                           const uint32_t *tile_seq, uint32_t n_seq, const ProbeTable &t,
-                           const uint64_t *filter, uint32_t filter_log2, uint4 *hot, uint4 *cold,
-                           uint64_t *hit_mask)
+static uint32_t probe_workgroups(const ProbeBatch &b) { return (uint32_t)((b.max_tiles + PROBE_WAVES - 1) / PROBE_WAVES); }
+/* the line probe strides over tiles when its grid is capped */
+static uint32_t line_workgroups(const ProbeBatch &b, const ProbeRun &r)
 {
-#define KGX_PROBE_M(M)                                                                               \
-    launch_probe_m<J, M>(grid, stream, residues, n_residues, seq_off, wbase, tile_seq, n_seq, t,     \
-                         filter, filter_log2, hot, cold, hit_mask)
-    if (mode == MODE_PACKED_KEY_FIRST)
-        KGX_PROBE_M(MODE_PACKED_KEY_FIRST);
-    else if (mode == MODE_PACKED)
-        KGX_PROBE_M(MODE_PACKED);
-    else if (mode == MODE_KEY_FIRST)
-        KGX_PROBE_M(MODE_KEY_FIRST);
-    else
-        KGX_PROBE_M(MODE_BUCKET);
-#undef KGX_PROBE_M
+    return r.max_blocks ? std::min<uint32_t>(probe_workgroups(b), r.max_blocks) : probe_workgroups(b);
 }
 
-hipError_t launch_probe(const uint8_t *residues, uint64_t n_residues, const uint64_t *seq_off,
-                        const uint64_t *wbase, const uint32_t *tile_seq, uint32_t n_seq,
-                        uint64_t max_tiles, const ProbeTable &t, int layout,
-                        const uint64_t *filter, uint32_t filter_log2,
-                        uint4 *hot, uint4 *cold, uint64_t *hit_mask, int probe_j, int variant,
-                        uint32_t lds_kb, uint32_t max_blocks, bool defer, hipStream_t stream, uint32_t nt)
+hipError_t launch_probe(const ProbeBatch &b, const ProbeTable &t, const ProbeHits &h, const ProbeRun &r,
+                        hipStream_t stream)
 {
-    if (max_tiles == 0)
+    constexpr int PACKED16 = KGX_LAYOUT_PACKED16;
+    if (b.max_tiles == 0)
         return hipSuccess;
-    if (t.home && layout != KGX_LAYOUT_PACKED16)
+    if (t.home && t.layout != PACKED16)
         return hipErrorInvalidValue; /* line-aligned homes exist for PACKED16 records only */
-    /* lds_kb > 0: each probe workgroup reserves that much LDS (unused beyond
-     * its own ~9 KB), capping the probe at 160 / lds_kb workgroups per CU so
-     * that other contexts' kernels find room beside it; the deferred form's
-     * list of open chains adds 512 B to a 128-window tile's 8960 */
-    const uint32_t own_lds = defer ? 9728u : 9216u;
-    const uint32_t dyn_lds = lds_kb * 1024u > own_lds ? lds_kb * 1024u - own_lds : 0u;
-    const dim3 grid((uint32_t)((max_tiles + PROBE_WAVES - 1) / PROBE_WAVES));
-    /* the line probe strides over tiles when its grid is capped */
-    const dim3 lgrid(max_blocks ? std::min<uint32_t>(grid.x, max_blocks) : grid.x);
-    if (variant == PROBE_AUTO && layout == KGX_LAYOUT_PACKED16 && !filter)
+    int variant = r.variant;
+    if (variant == PROBE_AUTO && t.layout == PACKED16 && !t.filter)
         variant = PROBE_LINE;
-    if ((variant == PROBE_LINE || variant == PROBE_LINE8) && layout == KGX_LAYOUT_PACKED16 && !filter) {
-#define KGX_LINE(JJ, GG)                                                                             \
-    launch_probe_line<JJ, GG>(lgrid, stream, residues, n_residues, seq_off, wbase, tile_seq, n_seq, t,  \
-                              hot, cold, hit_mask, dyn_lds, defer, nt);                              \
-    return hipGetLastError()
-        const int key = probe_j * 10 + (variant == PROBE_LINE8 ? 8 : 4);
-        switch (key) {
-        case 14: KGX_LINE(1, 4);
-        case 24: KGX_LINE(2, 4);
-        case 34: KGX_LINE(3, 4);
-        case 44: KGX_LINE(4, 4);
-        case 18: KGX_LINE(1, 8);
-        case 28: KGX_LINE(2, 8);
-        default: break; /* other tile sizes: the per-bucket kernel below */
-        }
-#undef KGX_LINE
+    if ((variant == PROBE_LINE || variant == PROBE_LINE8) && t.layout == PACKED16 && !t.filter) {
+        /* lds_kb > 0: each probe workgroup reserves that much LDS (unused
+         * beyond its own ~9 KB), capping the probe at 160 / lds_kb workgroups
+         * per CU so that other contexts' kernels find room beside it */
+        const uint32_t own_lds = r.defer ? PROBE_LINE_LDS_DEFER : PROBE_LINE_LDS;
+        const uint32_t dyn_lds = r.lds_kb * 1024u > own_lds ? r.lds_kb * 1024u - own_lds : 0u;
+        const auto line = [&](auto j, auto g) {
+            launch_probe_line<decltype(j)::value, decltype(g)::value, false>(
+                dim3(line_workgroups(b, r)), dyn_lds, b, t, h.hot, h.cold, h.hit_mask, r.defer, r.nt, stream);
+        };
+        /* tiles of 64-B lines: J 1-4; of 128-B lines: J 1-2 */
+        const bool known = variant == PROBE_LINE8
+                               ? with_constant<1, 2>(r.probe_j, [&](auto j) { line(j, std::integral_constant<int, 8>{}); })
+                               : with_constant<1, 2, 3, 4>(r.probe_j, [&](auto j) { line(j, std::integral_constant<int, 4>{}); });
+        if (known)
+            return hipGetLastError();
+        /* other tile sizes: the per-bucket kernel below */
     }
-    const bool kf = variant == PROBE_AUTO ? layout != KGX_LAYOUT_PACKED16 : variant == PROBE_KEY_FIRST;
-    const int mode = layout == KGX_LAYOUT_PACKED16 ? (kf ? MODE_PACKED_KEY_FIRST : MODE_PACKED)
-                                                   : (kf ? MODE_KEY_FIRST : MODE_BUCKET);
-#define KGX_PROBE_J(JJ)                                                                              \
-    launch_probe_j<JJ>(grid, stream, mode, residues, n_residues, seq_off, wbase, tile_seq, n_seq,   \
-                       t, filter, filter_log2, hot, cold, hit_mask)
-    switch (probe_j) {
-    case 1: KGX_PROBE_J(1); break;
-    case 2: KGX_PROBE_J(2); break;
-    case 3: KGX_PROBE_J(3); break;
-    case 4: KGX_PROBE_J(4); break;
-    case 5: KGX_PROBE_J(5); break;
-    case 8: KGX_PROBE_J(8); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef KGX_PROBE_J
-    return hipGetLastError();
+    const bool kf = variant == PROBE_AUTO ? t.layout != PACKED16 : variant == PROBE_KEY_FIRST;
+    const int mode = t.layout == PACKED16 ? (kf ? MODE_PACKED_KEY_FIRST : MODE_PACKED) : (kf ? MODE_KEY_FIRST : MODE_BUCKET);
+    const bool known = with_constant<1, 2, 3, 4, 5, 8>(r.probe_j, [&](auto j) {
+        with_constant<MODE_BUCKET, MODE_KEY_FIRST, MODE_PACKED, MODE_PACKED_KEY_FIRST>(mode, [&](auto m) {
+            launch_probe_bucket<decltype(j)::value, decltype(m)::value>(dim3(probe_workgroups(b)), b, t, h, stream);
+        });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-hipError_t launch_probe_dna(const uint8_t *bases, uint64_t n_bases, const uint64_t *anchor, const uint64_t *wbase,
-                            const uint32_t *tile_seq, uint32_t n_seq, uint64_t max_tiles, const ProbeTable &t,
-                            uint4 *hot, uint64_t *hit_mask, int probe_j, uint32_t max_blocks, bool defer,
+hipError_t launch_probe_dna(const ProbeBatch &b, const ProbeTable &t, const ProbeHits &h, const ProbeRun &r,
                             hipStream_t stream)
 {
-    if (max_tiles == 0)
+    if (b.max_tiles == 0)
         return hipSuccess;
-    const uint32_t tiles_grid = (uint32_t)((max_tiles + PROBE_WAVES - 1) / PROBE_WAVES);
-    const dim3 grid(max_blocks ? std::min<uint32_t>(tiles_grid, max_blocks) : tiles_grid);
-#define KGX_DNA(JJ)                                                                                  \
-    launch_probe_line<JJ, 4, true>(grid, stream, bases, n_bases, anchor, wbase, tile_seq, n_seq, t,  \
-                                   hot, nullptr, hit_mask, 0, defer);                                \
-    return hipGetLastError()
-    switch (probe_j) {
-    case 1: KGX_DNA(1);
-    case 2: KGX_DNA(2);
-    case 3: KGX_DNA(3);
-    case 4: KGX_DNA(4);
-    default: return hipErrorInvalidValue;
-    }
-#undef KGX_DNA
+    /* J 1-4, 64-B lines; no cold plane, LDS reservation or non-temporal stores */
+    const bool known = with_constant<1, 2, 3, 4>(r.probe_j, [&](auto j) {
+        launch_probe_line<decltype(j)::value, 4, true>(dim3(line_workgroups(b, r)), 0, b, t, h.hot, nullptr,
+                                                       h.hit_mask, r.defer, 0, stream);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace kgx

@@ -31,6 +31,20 @@ namespace kgx {
 
 /* sets the thread's kgx_last_error() text and returns code */
 int fail(int code, const std::string &msg);
+/* an on/off environment switch (KGX_LINE_HOME, KGX_LINE_MARKS, KGX_LINE_TWINS,
+ * KGX_PROBE_DEFER): "0" clears `value`; "1", unset or empty leaves it at its
+ * default; anything else is KGX_EINVAL, with `zero` and `one` naming the two
+ * settings */
+inline int env_switch(const char *name, const char *zero, const char *one, bool &value)
+{
+    const char *v = std::getenv(name);
+    if (!v || !*v || !std::strcmp(v, "1"))
+        return KGX_OK;
+    if (std::strcmp(v, "0"))
+        return fail(KGX_EINVAL, std::string(name) + ": 0 (" + zero + ") or 1 (" + one + "), not \"" + v + "\"");
+    value = false;
+    return KGX_OK;
+}
 bool is_gfx950(int dev);
 /* an image from n entries that are already in HBM of `device` (keys above
  * 20^8 skipped, the lowest index of a duplicated key wins): the device half
@@ -409,10 +423,10 @@ struct kgx_image {
     /* what the probes read: the line index when there is one */
     kgx::ProbeTable probe_table() const
     {
-        return lines ? kgx::ProbeTable{lines.records, 4 * lines.n_lines, lines.home_word()} : reference_table();
+        return lines ? kgx::ProbeTable{lines.records, 4 * lines.n_lines, lines.home_word(), layout} : reference_table();
     }
     /* the resident table under the reference's slots */
-    kgx::ProbeTable reference_table() const { return kgx::ProbeTable{resident(), num_sigs, 0u}; }
+    kgx::ProbeTable reference_table() const { return kgx::ProbeTable{resident(), num_sigs, 0u, layout}; }
 };
 
 struct kgx_ctx {
@@ -557,7 +571,10 @@ inline void drop_line_index(kgx_image *img)
 inline bool ctx_lines(const kgx_ctx *c) { return c->img->lines && c->opt.line_index; }
 inline ProbeTable ctx_probe_table(const kgx_ctx *c)
 {
-    return ctx_lines(c) ? c->img->probe_table() : c->img->reference_table();
+    ProbeTable t = ctx_lines(c) ? c->img->probe_table() : c->img->reference_table();
+    t.filter = c->opt.probe_filter ? c->img->d_filter : nullptr;
+    t.filter_log2_words = c->img->filter_log2_words;
+    return t;
 }
 /* a host batch's result: the context's host arrays */
 inline void fill_result(kgx_ctx *c, uint32_t n_seq, bool need_hits, bool want_best, uint64_t nwin, kgx_result *out)

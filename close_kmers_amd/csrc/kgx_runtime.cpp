@@ -940,11 +940,8 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
      * line run once, packed, after every slice's first round; 0, each slice
      * runs its own rounds.  An A/B switch, read here like KGX_SMALL_BATCH */
     bool probe_defer = true;
-    if (const char *pd = std::getenv("KGX_PROBE_DEFER"); pd && *pd) {
-        if (std::strcmp(pd, "0") && std::strcmp(pd, "1"))
-            return fail(KGX_EINVAL, std::string("KGX_PROBE_DEFER: 0 (rounds per slice) or 1 (deferred), not \"") + pd + "\"");
-        probe_defer = pd[0] == '1';
-    }
+    if (int rc = env_switch("KGX_PROBE_DEFER", "rounds per slice", "deferred", probe_defer))
+        return rc;
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
     c->probe_defer = probe_defer;
@@ -1157,6 +1154,24 @@ uint32_t probe_max_blocks(const kgx_ctx *c)
     return (uint32_t)c->opt.probe_persist * (uint32_t)cus;
 }
 
+/* what a probe launcher takes beside ctx_probe_table(c): c's planned batch
+ * over `bytes` (residues with offsets, or bases with anchors), its hit
+ * buffers, its options */
+struct CtxProbe {
+    ProbeBatch batch;
+    ProbeHits hits;
+    ProbeRun run;
+};
+CtxProbe ctx_probe(kgx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *starts)
+{
+    CtxProbe p;
+    p.batch = {bytes, n_bytes, starts, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(), c->n_seq, c->max_tiles};
+    p.hits = {c->hits.as<uint4>(), c->hits.as<uint4>() + c->hit_slots, c->hit_mask.as<uint64_t>()};
+    p.run = {(int)(c->tile_windows / 64), (int)c->opt.probe_variant, (uint32_t)c->opt.probe_lds_kb, probe_max_blocks(c),
+             c->probe_defer, (uint32_t)c->opt.probe_nt};
+    return p;
+}
+
 /* one probe launch on c's stream; with probe_serialize it waits for the
  * image's previous probe, whichever context issued it */
 template <class Launch>
@@ -1225,10 +1240,8 @@ int stage_probe_dna(kgx_ctx *c, const uint8_t *bases, uint64_t n_bases, const ui
         return fail(KGX_EINVAL, "fq probe: fragments without residues need the line probe on a PACKED16 image "
                                 "(set fq_residues 1 for other probes)");
     return probe_chained(c, [&] {
-        return launch_probe_dna(bases, n_bases, anchors, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(),
-                                c->n_seq, c->max_tiles, ctx_probe_table(c),
-                                c->hits.as<uint4>(), c->hit_mask.as<uint64_t>(), (int)(c->tile_windows / 64),
-                                probe_max_blocks(c), c->probe_defer, c->stream);
+        const CtxProbe p = ctx_probe(c, bases, n_bases, anchors);
+        return launch_probe_dna(p.batch, ctx_probe_table(c), p.hits, p.run, c->stream);
     });
 }
 
@@ -1241,12 +1254,8 @@ int kgx_stage_probe(kgx_ctx *c, const uint8_t *d_res, const uint64_t *d_off)
     if (!c || (!d_res && c->n_residues) || d_off != c->d_off)
         return fail(KGX_EINVAL, "probe: residues missing or offsets differ from the plan");
     return probe_chained(c, [&] {
-        return launch_probe(d_res, c->n_residues, d_off, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(),
-                            c->n_seq, c->max_tiles, ctx_probe_table(c), c->img->layout,
-                            c->opt.probe_filter ? c->img->d_filter : nullptr, c->img->filter_log2_words,
-                            c->hits.as<uint4>(), c->hits.as<uint4>() + c->hit_slots, c->hit_mask.as<uint64_t>(),
-                            (int)(c->tile_windows / 64), c->opt.probe_variant, (uint32_t)c->opt.probe_lds_kb,
-                            probe_max_blocks(c), c->probe_defer, c->stream, (uint32_t)c->opt.probe_nt);
+        const CtxProbe p = ctx_probe(c, d_res, c->n_residues, d_off);
+        return launch_probe(p.batch, ctx_probe_table(c), p.hits, p.run, c->stream);
     });
 }
 
