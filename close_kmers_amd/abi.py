@@ -21,6 +21,8 @@ ERRORS = {-1: "EINVAL", -2: "EIO", -3: "EFORMAT", -4: "ENOMEM", -5: "EDEVICE", -
 KGX_EBUSY = -8
 KGX_EDEVICE = -5
 KGX_EINVAL = -1
+KGX_EFORMAT = -3
+KGX_ERANGE = -6
 KGX_WAIT_SPIN, KGX_WAIT_SLEEP, KGX_WAIT_BLOCK = 0, 1, 2
 WANT_HITS, WANT_CALLS, WANT_OTU, WANT_BEST = 1, 2, 4, 8
 HIT_IN_RUN, HIT_OTU = 1, 2
@@ -94,6 +96,35 @@ class SigPass(ctypes.Structure):
 class RollupResult(ctypes.Structure):
     _fields_ = [("n_seq", ctypes.c_uint32), ("offsets", ctypes.c_void_p), ("rows", ctypes.c_void_p),
                 ("n_events", ctypes.c_uint64)]
+
+
+class InflateStats(ctypes.Structure):
+    """kgx_inflate_stats: what a deflate stream (or a body's members together) exercised."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("stored_blocks", "fixed_blocks", "dynamic_blocks", "max_code_len",
+                                               "max_distance", "max_length", "overlap", "matches")]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GunzipStats(ctypes.Structure):
+    _fields_ = [("inflate", InflateStats)] + \
+        [(k, ctypes.c_uint64) for k in ("members", "device_members", "host_blocked_members", "plain_members",
+                                        "bytes_in", "bytes_out")] + \
+        [(k, ctypes.c_float) for k in ("upload_ms", "kernel_ms", "download_ms")] + [("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_[1:-1]}
+        d.update(self.inflate.as_dict())
+        return d
+
+
+# kgx_gz_member / kgx_gz_status: the kernel's member table and per-member outcome
+GZ_MEMBER_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"),
+                            ("crc", "<u4"), ("reserved", "<u4")])
+GZ_STATUS_DTYPE = np.dtype([("reason", "<u4"), ("out_len", "<u4"), ("bit_pos", "<u8")])
+INFLATE_STATS_DTYPE = np.dtype([(k, "<u4") for k, _ in InflateStats._fields_])
+assert GZ_MEMBER_DTYPE.itemsize == 32 and GZ_STATUS_DTYPE.itemsize == 16 and INFLATE_STATS_DTYPE.itemsize == 32
 
 
 # kgx_rollup_row: LookupRequest's sequence_accumulated_score_t with its id
@@ -252,6 +283,13 @@ SIGNATURES = {
     "kgx_fq_create": (_INT, [_P, _CS, _CS, _CS, _CS, _PP]),
     "kgx_fq_destroy": (_INT, [_P]),
     "kgx_fq_process": (_INT, [_P, _CS, _U64, _INT, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_U64)]),
+    "kgx_inflate_host": (_INT, [_P, _U64, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                ctypes.POINTER(InflateStats), ctypes.POINTER(_U32), ctypes.POINTER(_U64)]),
+    "kgx_gunzip_scan": (_INT, [_P, _U64, _INT, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                               ctypes.POINTER(_U64)]),
+    "kgx_gunzip": (_INT, [_P, _P, _U64, _INT, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                          ctypes.POINTER(GunzipStats)]),
+    "kgx_gunzip_device": (_INT, [_P, _P, _P, _U32, _P, _P, _P, ctypes.POINTER(ctypes.c_float)]),
     "kgx_kmap_create": (_INT, [_INT, _INT, _PP]),
     "kgx_kmap_destroy": (_INT, [_P]),
     "kgx_kmap_add": (_INT, [_P, _P, _P, _U64]),
@@ -940,6 +978,59 @@ class FqHandler:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _bytes_ptr(b: bytes):
+    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) if b else None
+
+
+def inflate_host(raw: bytes, cap: int):
+    """kgx_inflate_host: one raw deflate stream on the calling thread, no device.
+    Returns (rc, output bytes, bytes of input used, InflateStats dict, reason, bit position)."""
+    raw = bytes(raw)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n, used, reason, bit = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64()
+    st = InflateStats()
+    rc = lib().kgx_inflate_host(_bytes_ptr(raw), len(raw), ctypes.addressof(out) if cap else None, cap,
+                                ctypes.byref(n), ctypes.byref(used), ctypes.byref(st), ctypes.byref(reason),
+                                ctypes.byref(bit))
+    return rc, out.raw[:n.value], used.value, st.as_dict(), reason.value, bit.value
+
+
+def gunzip_scan(gz: bytes, finished: bool = True) -> dict:
+    """kgx_gunzip_scan: framing only: members, blocked, out_bytes, consumed."""
+    gz = bytes(gz)
+    v = [ctypes.c_uint64() for _ in range(4)]
+    check(lib().kgx_gunzip_scan(_bytes_ptr(gz), len(gz), int(finished), *[ctypes.byref(x) for x in v]),
+          "kgx_gunzip_scan")
+    return dict(zip(("members", "blocked", "out_bytes", "consumed"), (x.value for x in v)))
+
+
+def gunzip(ctx: "Context | None", gz: bytes, finished: bool = True, cap: int | None = None):
+    """kgx_gunzip: (text, consumed, stats dict).  cap defaults to room for the
+    blocked members' ISIZEs; a body with plain members needs it given.  ctx None:
+    blocked members on host threads."""
+    gz = bytes(gz)
+    if cap is None:
+        cap = gunzip_scan(gz, finished)["out_bytes"]
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n, used = ctypes.c_uint64(), ctypes.c_uint64()
+    st = GunzipStats()
+    check(lib().kgx_gunzip(ctx.handle if ctx is not None else None, _bytes_ptr(gz), len(gz), int(finished),
+                           ctypes.addressof(out) if cap else None, cap, ctypes.byref(n), ctypes.byref(used),
+                           ctypes.byref(st)), "kgx_gunzip")
+    return out.raw[:n.value], used.value, st.as_dict()
+
+
+def gunzip_device(ctx: "Context", d_gz: int, members: np.ndarray, d_out: int):
+    """kgx_gunzip_device over device buffers: (rc, status[], member stats[], kernel ms)."""
+    members = np.ascontiguousarray(members, dtype=GZ_MEMBER_DTYPE)
+    status = np.zeros(len(members), GZ_STATUS_DTYPE)
+    stats = np.zeros(len(members), INFLATE_STATS_DTYPE)
+    ms = ctypes.c_float()
+    rc = lib().kgx_gunzip_device(ctx.handle, d_gz, members.ctypes.data, len(members), d_out, status.ctypes.data,
+                                 stats.ctypes.data, ctypes.byref(ms))
+    return rc, status, stats, ms.value
 
 
 def shard_cuts(offsets, n_shards: int) -> np.ndarray:

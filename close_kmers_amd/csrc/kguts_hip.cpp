@@ -2073,7 +2073,7 @@ FqRequest::FqBlock FqRequest::FqPart::view() const
  * again here from the true state.  So the reads, and the output, are the
  * sequential parse's.  One FamilyMapper serves the whole block, as the
  * reference keeps one per block (fq_process_request.cc:241). */
-void FqRequest::process(const char *text, size_t n, bool finished, std::ostream &os)
+void FqRequest::process_text(const char *text, size_t n, bool finished, std::ostream &os)
 {
     /* KGX_FQ_PART_KB: the part size, for tests of the parallel parse */
     const size_t kPartBytes = [] {
@@ -2343,8 +2343,117 @@ kgx_ctx *FqRequest::twin_ctx()
     return twin_;
 }
 
+/* The sniff, at the start of a request (parser in its start state, nothing
+ * carried): 1f 8b 08 makes the whole request gzip; a first block shorter than
+ * gzip's fixed header that begins with 1f is held until more arrives or the
+ * request ends.  A text request pays the sniff and nothing else. */
+void FqRequest::process(const char *block, size_t n, bool finished, std::ostream &os)
+{
+    if (body_ == BODY_UNKNOWN || body_ == BODY_HELD) {
+        const bool fresh = state_ == FQ_START && id_.empty() && seq_.empty();
+        const std::string &held = gz_tail_;
+        auto byte = [&](size_t i) { return (unsigned char)(i < held.size() ? held[i] : block[i - held.size()]); };
+        const size_t have = held.size() + n;
+        if (!fresh || have == 0 || byte(0) != 0x1f)
+            body_ = BODY_TEXT;
+        else if (have >= 3)
+            body_ = byte(1) == 0x8b && byte(2) == 8 ? BODY_GZIP : BODY_TEXT;
+        else if (finished)
+            body_ = BODY_TEXT;
+        else
+            body_ = BODY_HELD;
+        if (body_ == BODY_GZIP && have < 10 && !finished)
+            body_ = BODY_HELD;
+        if (body_ == BODY_HELD) {
+            gz_tail_.append(block, n);
+            return;
+        }
+        if (body_ == BODY_TEXT && !gz_tail_.empty()) { /* held bytes that were text after all */
+            std::string all;
+            all.swap(gz_tail_);
+            all.append(block, n);
+            if (finished)
+                body_ = BODY_UNKNOWN;
+            process_text(all.data(), all.size(), finished, os);
+            return;
+        }
+    }
+    const bool gzip = body_ == BODY_GZIP;
+    if (finished)
+        body_ = BODY_UNKNOWN; /* the next call starts a request */
+    if (gzip)
+        process_gzip(block, n, finished, os);
+    else
+        process_text(block, n, finished, os);
+}
+
+void FqRequest::process_gzip(const char *block, size_t n, bool finished, std::ostream &os)
+{
+    gz_tail_.append(block, n);
+    struct Reset { /* a request that ends, in its last block or in an error, leaves nothing behind */
+        FqRequest &r;
+        bool on, failed;
+        ~Reset()
+        {
+            if (on) {
+                r.gz_tail_.clear();
+                r.gz_members_ = 0;
+                r.body_ = BODY_UNKNOWN;
+            }
+            if (failed) { /* bad gzip data: the parser forgets the request too */
+                r.state_ = FQ_START;
+                r.id_.clear();
+                r.seq_.clear();
+            }
+        }
+    } reset{*this, true, true};
+    /* trailing bytes after a member that are no gzip are ignored, as gzip does */
+    if (gz_members_ && gz_tail_.size() >= 2 &&
+        !((unsigned char)gz_tail_[0] == 0x1f && (unsigned char)gz_tail_[1] == 0x8b))
+        gz_tail_.clear();
+    uint64_t members = 0, blocked = 0, out_bytes = 0, consumed = 0, out_len = 0;
+    int rc = kgx_gunzip_scan(gz_tail_.data(), gz_tail_.size(), finished, &members, &blocked, &out_bytes, &consumed);
+    if (rc)
+        throw_last(rc, "kgx_gunzip_scan");
+    /* blocked members state their sizes; a plain member's is found by trying */
+    size_t cap = (size_t)out_bytes + 64;
+    if (members > blocked && finished)
+        cap += 6 * gz_tail_.size() + (size_t(1) << 20);
+    for (;;) {
+        if (cap > gz_text_cap_) {
+            if (gz_text_)
+                kgx_host_free(gz_text_);
+            gz_text_ = nullptr;
+            gz_text_cap_ = 0;
+            void *q = nullptr;
+            if ((rc = kgx_host_alloc(cap, &q)))
+                throw_last(rc, "kgx_host_alloc");
+            gz_text_ = static_cast<char *>(q);
+            gz_text_cap_ = cap;
+        }
+        kgx_gunzip_stats gs;
+        rc = kgx_gunzip(kg_.ctx(), gz_tail_.data(), gz_tail_.size(), finished, gz_text_, gz_text_cap_, &out_len,
+                        &consumed, &gs);
+        if (rc == KGX_ERANGE && members > blocked) {
+            cap = gz_text_cap_ * 2;
+            continue;
+        }
+        if (rc)
+            throw_last(rc, "kgx_gunzip");
+        gz_members_ += gs.members;
+        break;
+    }
+    gz_tail_.erase(0, (size_t)consumed);
+    reset.on = finished;
+    reset.failed = false;
+    if (out_len || finished)
+        process_text(gz_text_, (size_t)out_len, finished, os);
+}
+
 FqRequest::~FqRequest()
 {
+    if (gz_text_)
+        kgx_host_free(gz_text_);
     if (twin_)
         kgx_ctx_destroy(twin_);
     if (twin2_)

@@ -564,7 +564,12 @@ public:
     FqRequest(const FqRequest &) = delete;
     FqRequest &operator=(const FqRequest &) = delete;
     /* one block of FASTQ text; `finished` = the request's last block
-     * (parse_complete).  Output lines are appended to os. */
+     * (parse_complete).  Output lines are appended to os.  A request whose
+     * first bytes are 1f 8b 08 is gzip, as the reference sniffs its first
+     * data (fq_process_request.cc:64-104): every block's complete members are
+     * inflated (kgx_gunzip) and their text processed as one block.  A plain
+     * (non-blocked) member is held until `finished`, which costs its
+     * compressed size in memory.  Bad gzip data throws Error(KGX_EFORMAT). */
     void process(const std::string &fastq_block, bool finished, std::ostream &os);
     void process(const char *fastq_block, size_t n, bool finished, std::ostream &os);
     /* reads already parsed (id, DNA) */
@@ -603,6 +608,9 @@ private:
         void parse(const char *a, const char *b);
         FqBlock view() const;
     };
+    /* one block of text (process() after the sniff and the inflate) */
+    void process_text(const char *text, size_t n, bool finished, std::ostream &os);
+    void process_gzip(const char *block, size_t n, bool finished, std::ostream &os);
     void process_block(const FqBlock &blk, FamilyMapper &mapper, std::ostream &os);
     /* process_block in two halves: launch sizes the block's fragments and
      * enqueues their lookup on ctx; finish collects the results and writes the
@@ -633,6 +641,13 @@ private:
     /* the exact re-parse after a rejected speculative cut: kept, so its pinned
      * buffer is allocated once, not per fallback */
     std::unique_ptr<FqPart> tail_;
+    /* gzip requests */
+    enum { BODY_UNKNOWN, BODY_HELD, BODY_TEXT, BODY_GZIP };
+    int body_ = BODY_UNKNOWN;  /* of the request in progress; BODY_HELD: fewer than 10 bytes so far, the first 1f */
+    std::string gz_tail_;      /* compressed bytes not consumed yet */
+    uint64_t gz_members_ = 0;  /* members inflated so far in this request */
+    char *gz_text_ = nullptr;  /* inflated text, pinned (kgx_host_alloc) */
+    size_t gz_text_cap_ = 0;
 };
 
 /* one host-buffer batch through kg's context, device results only (no D2H):

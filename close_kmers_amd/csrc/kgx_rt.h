@@ -330,6 +330,9 @@ bool probe_takes_dna(const kgx_ctx *c);
  * fragment a fragment pass emits has >= 11): window base = residue offset - 8
  * per earlier fragment, no scan; tile owners and the longest fragment as
  * launch_plan writes them (kgx_fq.hip) */
+/* kgx_inflate.hip: one wave per blocked gzip member */
+hipError_t launch_inflate_members(const uint8_t *gz, const kgx_gz_member *members, uint32_t n_members, uint8_t *out,
+                                  kgx_gz_status *status, kgx_inflate_stats *stats, hipStream_t stream);
 hipError_t launch_fq_plan(const uint64_t *off, uint32_t n, uint64_t *wbase, uint32_t *tile_seq, uint32_t tile_windows,
                           uint32_t *status, uint32_t *block_max, hipStream_t stream);
 
@@ -466,6 +469,12 @@ struct kgx_ctx {
     kgx::DevBuf fq_look; /* fq_fused: tile counter | tile states */
     kgx::PinnedVec<uint64_t> h_fq_tot; /* fragments, residues of the last fq batch */
     kgx::FqPending fq_pend;             /* an enqueued fragment pass awaiting its finish */
+    /* kgx_gunzip / kgx_gunzip_device (kgx_gunzip.cpp) */
+    kgx::DevBuf gz_in, gz_out, gz_members, gz_status, gz_stats;
+    kgx::PinnedVec<kgx_gz_member> h_gz_members;
+    kgx::PinnedVec<kgx_gz_status> h_gz_status;
+    kgx::PinnedVec<kgx_inflate_stats> h_gz_stats;
+    std::vector<hipEvent_t> gz_events; /* timing events: upload, kernel, download */
     /* kgx_fq_upload: reads whose H2D is enqueued, awaiting kgx_fq_fragments_uploaded */
     struct {
         bool active = false;

@@ -942,9 +942,19 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
     bool probe_defer = true;
     if (int rc = env_switch("KGX_PROBE_DEFER", "rounds per slice", "deferred", probe_defer))
         return rc;
+    /* KGX_GUNZIP_DEVICE=0|1: the default of option "gunzip_device" for new
+     * contexts (the handlers' own contexts have no other switch) */
+    int64_t gunzip_device = CtxOptions{}.gunzip_device;
+    if (const char *g = std::getenv("KGX_GUNZIP_DEVICE")) {
+        if (*g && std::strcmp(g, "0") && std::strcmp(g, "1"))
+            return fail(KGX_EINVAL, std::string("KGX_GUNZIP_DEVICE: 0 (host threads) or 1 (device), not \"") + g + "\"");
+        if (*g)
+            gunzip_device = *g == '1';
+    }
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
     c->probe_defer = probe_defer;
+    c->opt.gunzip_device = gunzip_device;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -999,6 +1009,8 @@ int kgx_ctx_destroy(kgx_ctx *c)
     for (hipEvent_t e : c->prof_ev)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : c->prof_done)
+        (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->gz_events)
         (void)hipEventDestroy(e);
     if (c->copy_stream) {
         (void)hipStreamSynchronize(c->copy_stream);

@@ -555,7 +555,13 @@ void *kgx_ctx_stream(kgx_ctx *ctx);
  * identical under every setting.  After a
  * chunked batch the device results are split over the two contexts:
  * kgx_kmap_add_hits / kgx_matrix_add_hits need a one-pass batch (host_chunks
- * 1, or want 0, which never chunks) */
+ * 1, or want 0, which never chunks).
+ * "gunzip_device" 1 / 0 (default): kgx_gunzip inflates blocked gzip members
+ * on the device / on up to 16 host threads (the same decoder source).  The
+ * device path is the faster one measured (17 against 5.8 GB/s of text, BGZF
+ * level 6); the default is 0 because it did not clear the
+ * bar set for it at level 1 (16 x one-thread zlib).  KGX_GUNZIP_DEVICE=0|1 in
+ * the environment sets the default of new contexts */
 int kgx_ctx_set_option(kgx_ctx *ctx, const char *name, int64_t value);
 /* counters of the context since its creation: "fused_batches" / "small_batches"
  * (small host batches that took the one-launch path / the one-wait path),
@@ -933,7 +939,9 @@ int kgx_fq_called_reads(kgx_ctx *ctx, const kgx_fragments *fragments, kgx_fq_cal
  * the family DB (KmerPegMapping::load_genus_map / load_families kmer.cc:
  * 341-493; NRLoader family mode nr_loader.cc:130-176, proteins in file
  * order).  Blocks are processed as the reference processes request blocks
- * (one FamilyMapper per block); `finished` marks the last block. */
+ * (one FamilyMapper per block); `finished` marks the last block.  A request
+ * whose first bytes are 1f 8b 08 is gzip (see below): each block's complete
+ * members are inflated (kgx_gunzip) and their text processed as a block. */
 typedef struct kgx_fq kgx_fq;
 int kgx_fq_create(kgx_image *img, const char *data_dir, const char *genus_file, const char *families_file,
                   const char *nr_fasta, kgx_fq **out);
@@ -941,6 +949,101 @@ int kgx_fq_destroy(kgx_fq *fq);
 /* *text: output lines of the block, owned by fq, valid until the next call */
 int kgx_fq_process(kgx_fq *fq, const char *fastq, uint64_t n, int finished, const char **text,
                    uint64_t *text_len);
+
+/* ---- gzip (RFC 1952) and DEFLATE (RFC 1951) -------------------------------
+ * The fq handler takes gzip bodies as the reference does
+ * (fq_process_request.cc:64-104: a request whose first bytes are 1f 8b is
+ * inflated before the FASTQ parser).  The decoder is the project's own
+ * (csrc/kgx_inflate.h), one source for host and device; no zlib is linked.
+ *
+ * A member is *blocked* (BGZF, what bgzip/htslib write) when its extra field
+ * holds a subfield "BC" of length 2: BSIZE = the member's total size - 1.  Its
+ * extent is known without decoding, its ISIZE is at most 65,536, and such
+ * members are inflated in parallel: one wave per member on the device
+ * (inflate_members_kernel, option "gunzip_device" 1), or one host thread per
+ * member ("gunzip_device" 0, the default).  A plain member's end is known only by decoding it; it is
+ * decoded on the host, serially.  CRC-32 and ISIZE are verified for every
+ * member.
+ *
+ * Behaviour where the reference is undefined: the reference's decoder stops at
+ * the first member's end (zlib_support.cc:85-96), so a multi-member body
+ * answers for its first member only and the rest is dropped silently.  Here
+ * every member is decoded and the texts are concatenated (RFC 1952 2.2, and
+ * what every gzip tool does); a single-member body gives the reference's
+ * bytes exactly.  After at least one member, bytes that do not begin with
+ * 1f 8b are ignored, as gzip ignores trailing garbage.
+ *
+ * Failure reasons (kgx_gz_status.reason, named in kgx_last_error()):
+ * 1 block type 3, 2 stored LEN != ~NLEN, 3 over-subscribed code lengths,
+ * 4 incomplete code lengths, 5 repeat with no previous length, 6 repeat past
+ * HLIT + HDIST, 7 no end-of-block code, 8 length / distance symbol above
+ * 285 / 29, 9 HLIT / HDIST too large, 10 invalid code, 11 distance before the
+ * member's start, 12 input ends inside the stream, 13 output longer than
+ * ISIZE (or than the room given), 14 output shorter than ISIZE, 15 CRC-32
+ * mismatch; framing: 32 not gzip, 33 method not deflate, 34 reserved flag
+ * bits, 35 member cut short, 36 BSIZE does not cover header and trailer,
+ * 37 blocked member with ISIZE above 65,536, 38 header CRC. */
+typedef struct kgx_inflate_stats {
+    uint32_t stored_blocks, fixed_blocks, dynamic_blocks; /* blocks by type */
+    uint32_t max_code_len; /* longest code length of a dynamic block's codes */
+    uint32_t max_distance; /* largest match distance used */
+    uint32_t max_length;   /* longest match */
+    uint32_t overlap;      /* 1: some match overlapped its own output (distance < length) */
+    uint32_t matches;
+} kgx_inflate_stats;
+typedef struct kgx_gz_member { /* one blocked member for the kernel */
+    uint64_t in_off;  /* its deflate data (after the header) in the compressed bytes */
+    uint64_t out_off; /* its slot in the output: the exclusive scan of the ISIZEs */
+    uint32_t in_len;  /* deflate bytes (up to the trailer) */
+    uint32_t out_len; /* ISIZE */
+    uint32_t crc;     /* CRC-32 from the trailer */
+    uint32_t reserved;
+} kgx_gz_member;
+typedef struct kgx_gz_status {
+    uint32_t reason;  /* 0 = the member's bytes are in its slot and its CRC matched */
+    uint32_t out_len; /* bytes produced */
+    uint64_t bit_pos; /* input bit position (within the member's deflate data) of a failure */
+} kgx_gz_status;
+typedef struct kgx_gunzip_stats {
+    kgx_inflate_stats inflate; /* over all members: counts summed, the others the maximum */
+    uint64_t members, device_members, host_blocked_members, plain_members;
+    uint64_t bytes_in, bytes_out;
+    float upload_ms, kernel_ms, download_ms; /* event times of the device path */
+    uint32_t reserved;
+} kgx_gunzip_stats;
+/* One raw deflate stream gz[0, n) into out[0, cap) on the calling thread; no
+ * device needed.  KGX_OK, or KGX_EFORMAT with *reason and *bit_pos (out_len =
+ * the bytes before the failure).  in_used = bytes of gz the stream took. */
+int kgx_inflate_host(const void *gz, uint64_t n, void *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used,
+                     kgx_inflate_stats *stats, uint32_t *reason, uint64_t *bit_pos);
+/* Framing only, no device: the complete blocked members at the front of
+ * gz[0, n).  blocked = their number, out_bytes = the sum of their ISIZEs,
+ * consumed = their bytes; members = blocked, plus 1 when the walk stopped at
+ * a plain member's header.  A blocked member that is not complete yet stays
+ * unconsumed; with `finished` it is KGX_EFORMAT.  Trailing bytes after at
+ * least one member that do not begin with 1f 8b are consumed and ignored. */
+int kgx_gunzip_scan(const void *gz, uint64_t n, int finished, uint64_t *members, uint64_t *blocked,
+                    uint64_t *out_bytes, uint64_t *consumed);
+/* gz[0, n) -> out[0, cap), host buffers.  Every complete member is decoded,
+ * in order, the texts concatenated; consumed never splits a member.  Blocked
+ * members go up to the device, through the kernel and back on ctx's stream
+ * (option "gunzip_device" 1; 0, the default, and ctx NULL: up to 16 host threads); plain members are
+ * decoded on the host, and only with `finished`: without it the walk stops in
+ * front of a plain member (its end is not known), which costs the caller its
+ * compressed size in memory until the last block.  cap too small: KGX_ERANGE,
+ * nothing written past cap.  Bad data: KGX_EFORMAT, kgx_last_error() naming
+ * the member index, the reason and the bit position.  stats may be NULL. */
+int kgx_gunzip(kgx_ctx *ctx, const void *gz, uint64_t n, int finished, void *out, uint64_t cap, uint64_t *out_len,
+               uint64_t *consumed, kgx_gunzip_stats *stats);
+/* The kernel alone over device buffers: members[] (host) describes n_members
+ * blocked members of d_gz; member m's bytes go to d_out + out_off.  status[]
+ * (host, n_members) gets every member's outcome, member_stats[] (host, may be
+ * NULL) its statistics, *kernel_ms (may be NULL) the kernel's event time.
+ * d_gz must hold every [in_off, in_off + in_len) and d_out every [out_off,
+ * out_off + out_len): the kernel touches nothing else.  KGX_OK, or KGX_EFORMAT
+ * when some member failed (the others' outputs are intact). */
+int kgx_gunzip_device(kgx_ctx *ctx, const void *d_gz, const kgx_gz_member *members, uint32_t n_members, void *d_out,
+                      kgx_gz_status *status, kgx_inflate_stats *member_stats, float *kernel_ms);
 
 /* ---- k-mer -> id tables in HBM ------------------------------------------
  * KmerPegMapping's kmer_to_id_ (kmer.h:84-127, filled by /add through

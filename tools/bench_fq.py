@@ -86,6 +86,9 @@ def main():
                     help="kgx_image_set_line_index load (keys per 64 lines; 0 = probe the reference slots)")
     ap.add_argument("--fq-residues", type=int, default=0,
                     help="1 = fragments with residues + the residue probe; 0 (default) = anchors + the DNA probe")
+    ap.add_argument("--gzip", choices=("bgzf", "plain"), default=None,
+                    help="also run the handler on the same text compressed (BGZF members of 65,280 bytes, or one "
+                         "plain gzip member; level 6, compressed here and not timed), beside the text input")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a context option (kgx_ctx_set_option) on every worker context, e.g. probe_j=3")
     args = ap.parse_args()
@@ -236,6 +239,27 @@ def main():
                 out = handler_pass(fq)
                 th.append(time.perf_counter() - t0)
             t_h = float(np.median(th))
+            gz_line = None
+            if args.gzip:
+                import gzip as _gzip
+                sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+                from bench_gunzip import bgzf_bytes
+                t0 = time.time()
+                gz = bgzf_bytes(text) if args.gzip == "bgzf" else _gzip.compress(text, 6)
+                t_c = time.time() - t0
+                fq.process(gz, True)  # warm (buffer growth)
+                tg = []
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    out_gz = fq.process(gz, True)
+                    tg.append(time.perf_counter() - t0)
+                # the text input as one block, for the same FamilyMapper span
+                one = [fq.process(text, True) for _ in range(1)][0]
+                gz_line = {"kind": args.gzip, "compressed_bytes": len(gz), "compress_s": t_c,
+                           "reads_per_s": hn / float(np.median(tg)), "ms": [t * 1e3 for t in tg],
+                           "same_output_as_text": bool(out_gz == one),
+                           "note": "the whole compressed body in one kgx_fq_process call: inflate, then the text "
+                                   "handler (no overlap between the two)"}
         del blocks
     line = {
         "metric": "fq_process_request reads/s: 6-frame translate + lookup (C4)",
@@ -248,6 +272,8 @@ def main():
                     "fastq_bytes": len(text), "blocks": -(-len(text) // blk), "block_bytes": blk,
                     "note": "FASTQ text -> output text through kgx_fq_process (host text in, host text out)"},
     }
+    if gz_line:
+        line["handler_gzip"] = gz_line
     if not args.no_cpu_baseline:
         import oracle
         oracle.build(ref=False)
