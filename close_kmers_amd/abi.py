@@ -93,6 +93,21 @@ class SigPass(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+LABEL_OTHER, LABEL_NONE = -1, -2
+RECALL_STAGES = ("upload", "pass", "tally", "download")
+RECALL_LABEL_CLASSES = ("kept", "other", "none")
+RECALL_CALL_CLASSES = ("match", "mismatch", "ambiguous", "none")
+RECALL_FUNCTION_DTYPE = np.dtype([("labelled", "<u4"), ("correct", "<u4"), ("called", "<u4")])
+RECALL_PAIR_DTYPE = np.dtype([("label", "<i4"), ("called", "<i4"), ("count", "<u8")])
+
+
+class RecallStats(ctypes.Structure):
+    """kgx_recall_stats: cell[label class][call class]."""
+    _fields_ = [("n_seq", ctypes.c_uint64), ("cell", (ctypes.c_uint64 * 4) * 3), ("n_changed", ctypes.c_uint64),
+                ("n_confusions", ctypes.c_uint64), ("n_pieces", ctypes.c_uint32),
+                ("stage_ms", ctypes.c_float * len(RECALL_STAGES))]
+
+
 class RollupResult(ctypes.Structure):
     _fields_ = [("n_seq", ctypes.c_uint32), ("offsets", ctypes.c_void_p), ("rows", ctypes.c_void_p),
                 ("n_events", ctypes.c_uint64)]
@@ -354,6 +369,13 @@ SIGNATURES = {
     "kgx_sig_image": (_INT, [_P, _U64, _PP, ctypes.POINTER(_U64)]),
     "kgx_sig_stage_ms": (_INT, [_P, ctypes.POINTER(ctypes.c_float)]),
     "kgx_sig_destroy": (_INT, [_P]),
+    "kgx_recall_run": (_INT, [_P, ctypes.POINTER(Params), _P, _P, _P, _U32, _U32, _U64, _PP]),
+    "kgx_recall_stats_get": (_INT, [_P, ctypes.POINTER(RecallStats)]),
+    "kgx_recall_best": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
+    "kgx_recall_functions": (_INT, [_P, _PP, ctypes.POINTER(_U32)]),
+    "kgx_recall_changed": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
+    "kgx_recall_confusions": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
+    "kgx_recall_destroy": (_INT, [_P]),
 }
 
 
@@ -838,6 +860,74 @@ class Context:
     def close(self) -> None:
         if self.handle:
             lib().kgx_ctx_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Recall:
+    """Labelled sequences back through ctx's image, compared and tallied on the
+    device (kgx_recall_run): labels[i] is an index into the function index,
+    LABEL_OTHER or LABEL_NONE.  piece_residues bounds the residues of one piece
+    of whole sequences (0: the library's default); no result depends on it."""
+
+    def __init__(self, ctx: Context, residues, offsets, labels, n_functions: int,
+                 params: Params | dict | None = None, piece_residues: int = 0):
+        residues, offsets, params = _batch_args(residues, offsets, params)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if len(offsets) != len(lab) + 1:
+            raise ValueError("offsets holds one entry more than labels")
+        h = ctypes.c_void_p()
+        check(lib().kgx_recall_run(ctx.handle, ctypes.byref(params), residues.ctypes.data if residues.size else None,
+                                   offsets.ctypes.data, lab.ctypes.data if lab.size else None, len(lab), n_functions,
+                                   piece_residues, ctypes.byref(h)), "kgx_recall_run")
+        self.handle = h.value
+
+    def _stats(self) -> RecallStats:
+        s = RecallStats()
+        check(lib().kgx_recall_stats_get(self.handle, ctypes.byref(s)), "kgx_recall_stats_get")
+        return s
+
+    def stats(self) -> dict:
+        """n_seq, n_changed, n_confusions, n_pieces and cell, a 3 x 4 uint64
+        array of label class (kept, other, none) x call class (match, mismatch,
+        ambiguous, none)."""
+        s = self._stats()
+        cell = np.array([[s.cell[i][j] for j in range(4)] for i in range(3)], np.uint64)
+        return {"n_seq": s.n_seq, "cell": cell, "n_changed": s.n_changed, "n_confusions": s.n_confusions,
+                "n_pieces": s.n_pieces}
+
+    def stage_ms(self) -> dict:
+        return dict(zip(RECALL_STAGES, (float(x) for x in self._stats().stage_ms)))
+
+    def _array(self, fn, what: str, dtype, count_type=_U64) -> np.ndarray:
+        p, n = ctypes.c_void_p(), count_type()
+        check(fn(self.handle, ctypes.byref(p), ctypes.byref(n)), what)
+        return _view(p.value, n.value, dtype)
+
+    def best(self) -> np.ndarray:
+        """The best call of every sequence (BEST_DTYPE), in input order."""
+        return self._array(lib().kgx_recall_best, "kgx_recall_best", BEST_DTYPE)
+
+    def functions(self) -> np.ndarray:
+        """labelled, correct, called per function (RECALL_FUNCTION_DTYPE)."""
+        return self._array(lib().kgx_recall_functions, "kgx_recall_functions", RECALL_FUNCTION_DTYPE, _U32)
+
+    def changed(self) -> np.ndarray:
+        """Ascending indices of the sequences whose call differs from their label."""
+        return self._array(lib().kgx_recall_changed, "kgx_recall_changed", np.uint32)
+
+    def confusions(self) -> np.ndarray:
+        """Distinct (label, called) of the mislabelled calls with their counts, ascending."""
+        return self._array(lib().kgx_recall_confusions, "kgx_recall_confusions", RECALL_PAIR_DTYPE)
+
+    def close(self) -> None:
+        if self.handle:
+            lib().kgx_recall_destroy(self.handle)
             self.handle = None
 
     def __enter__(self):

@@ -17,6 +17,11 @@ The front end of build_signature_kmers.cc over the device selection
     the reference's placeholder `genomes` file and kmer.table.mem_map, the
     files KmerImage / kgx_image_open and the handlers read.
 
+--recall-output DIR and --validation-folder DIR run the builder's last step,
+the recall of the training proteins and the validation of held-out genomes, on
+the image just built, before it is closed (close_kmers_amd/recall.py,
+DESIGN.md §8.9).
+
 Left out, as in DESIGN.md §8.8: good roles (a function kept because one of its
 roles is listed), stripping of function comments ("# ..." / "! ..." tails),
 and functions or genome names taken from FASTA definition lines (the
@@ -24,7 +29,8 @@ and functions or genome names taken from FASTA definition lines (the
 
     python -m close_kmers_amd.signatures --definitions defs.tsv [more.tsv ...] \\
         --fasta genome1.fa genome2.fa ... [--min-reps 5] [--keep-function NAME ...] --out DIR \\
-        [--max-pass-tuples N]
+        [--max-pass-tuples N] [--recall-output DIR] [--validation-folder DIR [--validation-verbose]] \\
+        [--recall-min-hits 5] [--recall-max-gap 200]
 
 A corpus whose tuples do not fit the device at once is selected in passes over
 key ranges with the same result; --max-pass-tuples bounds a
@@ -117,11 +123,17 @@ def write_indexes(out_dir: str, functions: list[bytes]) -> None:
 
 
 def build_data_dir(definitions, fastas, out_dir: str, min_reps: int = 5, keep=(), device: int = 0,
-                   num_sigs: int = 0, max_pass_tuples: int = 0) -> dict:
+                   num_sigs: int = 0, max_pass_tuples: int = 0, recall_output: str | None = None,
+                   validation_folder: str | None = None, validation_verbose: bool = False,
+                   recall_min_hits: int = 5, recall_max_gap: int = 200) -> dict:
     """Runs the whole builder on `device`; returns the selection's statistics
     with n_functions, n_stored and n_passes added.  max_pass_tuples: the most
-    tuples one pass of the selection holds (0: what the device holds)."""
-    from . import abi
+    tuples one pass of the selection holds (0: what the device holds).
+    recall_output / validation_folder: the image, while it is still held, also
+    recalls the corpus into that directory / validates that folder's genomes
+    (recall.recall, recall.validate); the totals are returned under "recall" /
+    "validation"."""
+    from . import abi, recall
     id_function = read_definitions(definitions)
     records = [read_fasta(p) for p in fastas]
     functions = kept_functions(id_function, [[rid for rid, _ in recs] for recs in records], min_reps, keep)
@@ -133,6 +145,15 @@ def build_data_dir(definitions, fastas, out_dir: str, min_reps: int = 5, keep=()
         img, stored = sig.image(num_sigs)
         with img:
             img.save(out_dir)
+            if recall_output or validation_folder:
+                params = {"min_hits": recall_min_hits, "max_gap": recall_max_gap}
+                with abi.Context(img) as ctx:
+                    if recall_output:
+                        stats["recall"] = recall.recall(ctx, recall_output, fastas, records, id_function, functions,
+                                                        params)
+                    if validation_folder:
+                        stats["validation"] = recall.validate(ctx, validation_folder, functions, params,
+                                                              validation_verbose)
     stats.update(n_functions=len(functions), n_stored=stored, n_passes=n_passes)
     return stats
 
@@ -148,9 +169,12 @@ def main(argv=None) -> int:
     ap.add_argument("--num-sigs", type=int, default=0, help="table size (default: the builder's prime rule)")
     ap.add_argument("--max-pass-tuples", type=int, default=0,
                     help="most tuples held on the device at once (default: what it holds, at most 2^31-1)")
+    from . import recall
+    recall.add_arguments(ap)
     a = ap.parse_args(argv)
     stats = build_data_dir(a.definitions, a.fasta, a.out, a.min_reps, a.keep_function, a.device, a.num_sigs,
-                           a.max_pass_tuples)
+                           a.max_pass_tuples, a.recall_output, a.validation_folder, a.validation_verbose,
+                           a.recall_min_hits, a.recall_max_gap)
     print(json.dumps(stats))
     return 0
 

@@ -437,6 +437,64 @@ int kgx_sig_image(kgx_sig *s, uint64_t num_sigs, kgx_image **out, uint64_t *n_st
 int kgx_sig_stage_ms(const kgx_sig *s, float *ms);
 int kgx_sig_destroy(kgx_sig *s);
 
+/* ---- recall: labelled proteins back through an image ---- */
+/* build_signature_kmers.cc's --recall-output / --validation-folder pass on
+ * the device: every sequence runs through the context's image with
+ * KGX_WANT_BEST, its best call is compared with its label, and the tallies
+ * are made in HBM; hits and calls never reach the host.  seq_label[i] is an
+ * index into the function index (>= 0), KGX_LABEL_OTHER (the id has a
+ * function that is not in the index) or KGX_LABEL_NONE (the id has none).
+ * Call classes, from kgx_best_call.kind: match (kind 1, fi0 == label),
+ * mismatch (kind 1 otherwise), ambiguous (kind 2), none (kinds 0 and 3);
+ * label classes: kept (>= 0), other, none. */
+#define KGX_LABEL_OTHER (-1)
+#define KGX_LABEL_NONE (-2)
+#define KGX_RECALL_STAGES 4
+typedef struct kgx_recall kgx_recall;
+typedef struct kgx_recall_stats {
+    uint64_t n_seq;
+    uint64_t cell[3][4]; /* [label class][call class] in the orders above */
+    uint64_t n_changed;
+    uint64_t n_confusions;
+    uint32_t n_pieces;
+    float stage_ms[KGX_RECALL_STAGES]; /* upload, pass, tally, download; summed over the pieces */
+} kgx_recall_stats;
+typedef struct kgx_recall_function {
+    uint32_t labelled; /* sequences labelled with the function */
+    uint32_t correct;  /* of those, the matches */
+    uint32_t called;   /* kind-1 calls of the function, whatever the label */
+} kgx_recall_function;
+typedef struct kgx_recall_pair {
+    int32_t label, called;
+    uint64_t count;
+} kgx_recall_pair;
+/* residues / seq_offsets as in kgx_process_batch (offsets need not start at
+ * 0; a sequence is cut at its first NUL byte).  The corpus runs in pieces of
+ * whole consecutive sequences: a piece is closed before the sequence that
+ * would take its residues above piece_residues, so a longer sequence is a
+ * piece of its own (0: 2^25 residues).  No result depends on the pieces.
+ * Synchronous.  KGX_EINVAL for a null argument, offsets that decrease, or a
+ * label below -2 or not below n_functions; KGX_ERANGE for more than 2^31-1
+ * sequences, a piece above 2^40 residues, or a called function (fi0, fi1)
+ * not below n_functions -- the image then belongs to another function index;
+ * nothing is written out of bounds and no result is returned; KGX_EDEVICE
+ * when the context's device is not gfx950.  n_seq 0 gives an empty result. */
+int kgx_recall_run(kgx_ctx *ctx, const kgx_params *params, const char *residues, const uint64_t *seq_offsets,
+                   const int32_t *seq_label, uint32_t n_seq, uint32_t n_functions, uint64_t piece_residues,
+                   kgx_recall **out);
+int kgx_recall_stats_get(const kgx_recall *r, kgx_recall_stats *out);
+/* host views, valid until kgx_recall_destroy: the n_seq best calls in input
+ * order; n_functions tallies; the changed sequences' indices, ascending (the
+ * reference's "New" rows: call class none with a label other than
+ * KGX_LABEL_NONE, kind 1 with fi0 != label, every kind 2); the distinct
+ * (label, called) pairs of the kept / mismatch sequences, ascending by label,
+ * then by called */
+int kgx_recall_best(const kgx_recall *r, const kgx_best_call **best, uint64_t *n);
+int kgx_recall_functions(const kgx_recall *r, const kgx_recall_function **fn, uint32_t *n);
+int kgx_recall_changed(const kgx_recall *r, const uint32_t **seq, uint64_t *n);
+int kgx_recall_confusions(const kgx_recall *r, const kgx_recall_pair **pairs, uint64_t *n);
+int kgx_recall_destroy(kgx_recall *r);
+
 /* ---- contexts: one per host thread, like one KmerGuts per pool thread --- */
 /* The environment variable KGX_PROBE_DEFER, read when a context is created,
  * picks the form of its line probe over a line index with marks: 1 or unset,
