@@ -108,6 +108,17 @@ class RecallStats(ctypes.Structure):
                 ("stage_ms", ctypes.c_float * len(RECALL_STAGES))]
 
 
+UNIQ_STAGES = ("upload", "pass", "sets", "group", "download")
+
+
+class UniqStats(ctypes.Structure):
+    """kgx_uniq_stats."""
+    _fields_ = ([(k, ctypes.c_uint64) for k in ("n_seq", "n_hits", "n_set_keys", "n_groups", "n_empty",
+                                                "largest_group", "list_compares")] +
+                [("n_pieces", ctypes.c_uint32), ("digest_bits", ctypes.c_uint32),
+                 ("stage_ms", ctypes.c_float * len(UNIQ_STAGES))])
+
+
 class RollupResult(ctypes.Structure):
     _fields_ = [("n_seq", ctypes.c_uint32), ("offsets", ctypes.c_void_p), ("rows", ctypes.c_void_p),
                 ("n_events", ctypes.c_uint64)]
@@ -376,6 +387,12 @@ SIGNATURES = {
     "kgx_recall_changed": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
     "kgx_recall_confusions": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
     "kgx_recall_destroy": (_INT, [_P]),
+    "kgx_uniq_run": (_INT, [_P, _P, _P, _U32, _U64, _U32, _PP]),
+    "kgx_uniq_stats_get": (_INT, [_P, ctypes.POINTER(UniqStats)]),
+    "kgx_uniq_groups": (_INT, [_P, _PP, _PP, ctypes.POINTER(_U64)]),
+    "kgx_uniq_group_of": (_INT, [_P, _PP, ctypes.POINTER(_U64)]),
+    "kgx_uniq_sets": (_INT, [_P, _PP, _PP, ctypes.POINTER(_U64)]),
+    "kgx_uniq_destroy": (_INT, [_P]),
 }
 
 
@@ -928,6 +945,70 @@ class Recall:
     def close(self) -> None:
         if self.handle:
             lib().kgx_recall_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Unique:
+    """Sequences grouped by the set of signature k-mers ctx's image hits in
+    them, on the device (kgx_uniq_run; unique_prots.cc).  Groups stand in the
+    order of std::map<std::set<u64>, ...>, members in input order.
+    piece_residues bounds the residues of one piece of whole sequences (0: the
+    library's default) and digest_bits (0..64) the digest the grouping sort
+    orders by before it compares lists; no result depends on either."""
+
+    def __init__(self, ctx: Context, residues, offsets, piece_residues: int = 0, digest_bits: int = 64):
+        residues, offsets, _ = _batch_args(residues, offsets, None)
+        if len(offsets) < 1:
+            raise ValueError("offsets holds one entry more than there are sequences")
+        h = ctypes.c_void_p()
+        check(lib().kgx_uniq_run(ctx.handle, residues.ctypes.data if residues.size else None, offsets.ctypes.data,
+                                 len(offsets) - 1, piece_residues, digest_bits, ctypes.byref(h)), "kgx_uniq_run")
+        self.handle = h.value
+
+    def _stats(self) -> UniqStats:
+        s = UniqStats()
+        check(lib().kgx_uniq_stats_get(self.handle, ctypes.byref(s)), "kgx_uniq_stats_get")
+        return s
+
+    def stats(self) -> dict:
+        """n_seq, n_hits, n_set_keys, n_groups, n_empty, largest_group,
+        list_compares, n_pieces, digest_bits."""
+        s = self._stats()
+        return {k: int(getattr(s, k)) for k, _ in UniqStats._fields_ if k != "stage_ms"}
+
+    def stage_ms(self) -> dict:
+        return dict(zip(UNIQ_STAGES, (float(x) for x in self._stats().stage_ms)))
+
+    def _csr(self, fn, what: str, dtype):
+        off, val, n = ctypes.c_void_p(), ctypes.c_void_p(), _U64()
+        check(fn(self.handle, ctypes.byref(off), ctypes.byref(val), ctypes.byref(n)), what)
+        offsets = _view(off.value, n.value + 1, np.uint64)
+        return offsets, _view(val.value, int(offsets[-1]), dtype)
+
+    def groups(self):
+        """(group_offsets, members): the groups as a CSR of sequence indices,
+        ascending within a group."""
+        return self._csr(lib().kgx_uniq_groups, "kgx_uniq_groups", np.uint32)
+
+    def group_of(self) -> np.ndarray:
+        """Each sequence's group."""
+        p, n = ctypes.c_void_p(), _U64()
+        check(lib().kgx_uniq_group_of(self.handle, ctypes.byref(p), ctypes.byref(n)), "kgx_uniq_group_of")
+        return _view(p.value, n.value, np.uint32)
+
+    def sets(self):
+        """(set_offsets, keys): each group's ascending key list, in group order."""
+        return self._csr(lib().kgx_uniq_sets, "kgx_uniq_sets", np.uint64)
+
+    def close(self) -> None:
+        if self.handle:
+            lib().kgx_uniq_destroy(self.handle)
             self.handle = None
 
     def __enter__(self):

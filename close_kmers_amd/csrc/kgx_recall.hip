@@ -169,9 +169,13 @@ struct RecallEvents {
     }
 };
 
+}  // namespace
+
+namespace kgx {
+
 /* as the host batches cut (kgx_host_batch.cpp cut_at_nul): from the residue
  * before the first NUL on, a staged sequence reads 'X' */
-void recall_cut_at_nul(char *b, uint64_t len)
+static void recall_cut_at_nul(char *b, uint64_t len)
 {
     const void *z = len ? std::memchr(b, 0, len) : nullptr;
     if (!z)
@@ -225,6 +229,10 @@ int recall_stage_upload(kgx_ctx *c, const char *src, uint64_t n, const uint64_t 
     HIP_TRY(hipMemcpyAsync(c->residues.p, dst, n, hipMemcpyHostToDevice, c->stream));
     return KGX_OK;
 }
+
+}  // namespace kgx
+
+namespace {
 
 /* the run's device arrays */
 struct RecallDev {

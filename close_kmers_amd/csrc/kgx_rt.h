@@ -624,6 +624,10 @@ int expand_chunk(const kgx_hit_chunk &ch, const uint64_t *hoff, const char *resi
 /* kgx_compact_expand with a choice of streaming stores */
 int compact_expand(const kgx_compact_result *r, const char *residues, const uint64_t *seq_offsets, uint32_t s_begin,
                    uint32_t s_end, uint32_t seq_base, kgx_hit *out, bool nt);
+/* a corpus piece's n residues from the caller's src into c's pinned staging
+ * and up to c->residues on c's stream, each sequence cut at its first NUL
+ * (off: the piece's m + 1 absolute offsets); kgx_recall.hip */
+int recall_stage_upload(kgx_ctx *c, const char *src, uint64_t n, const uint64_t *off, uint32_t m);
 }  // namespace kgx
 
 #endif

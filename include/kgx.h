@@ -495,6 +495,44 @@ int kgx_recall_changed(const kgx_recall *r, const uint32_t **seq, uint64_t *n);
 int kgx_recall_confusions(const kgx_recall *r, const kgx_recall_pair **pairs, uint64_t *n);
 int kgx_recall_destroy(kgx_recall *r);
 
+/* ---- unique_prots: proteins grouped by their signature k-mer sets ---- */
+/* unique_prots.cc on the device.  A sequence's set is the set of distinct
+ * which_kmer values of its hits, taken before any scoring rule (no
+ * kgx_params).  Sequences with equal sets form a group; members stand in
+ * input order; groups are ordered as std::map orders std::set<u64> keys:
+ * the ascending key lists compared lexicographically, a proper prefix before
+ * the longer list, so the empty set's group, when there is one, is first.
+ * Two sequences share a group iff their lists are equal key by key:
+ * digest_bits (0..64) only sets how many bits of a list digest order the
+ * grouping sort before lists are compared, and changes no result.
+ * residues / seq_offsets / piece_residues as in kgx_recall_run; a piece is
+ * also closed at 2^29 sequences.  Hits never reach the host.  Synchronous.
+ * KGX_EINVAL for a null argument, offsets that decrease or digest_bits > 64;
+ * KGX_ERANGE for more than 2^31-1 sequences or a piece of more than 2^31-1
+ * residues; KGX_ENOMEM when the corpus's key lists do not fit the device;
+ * KGX_EDEVICE when the context's device is not gfx950.  n_seq 0 gives an
+ * empty result. */
+#define KGX_UNIQ_STAGES 5 /* upload, pass (plan + probe), sets, group, download */
+typedef struct kgx_uniq kgx_uniq;
+typedef struct kgx_uniq_stats {
+    uint64_t n_seq, n_hits, n_set_keys; /* hits before, keys after the per-sequence unique */
+    uint64_t n_groups, n_empty, largest_group;
+    uint64_t list_compares; /* comparator calls of the grouping sort that had to walk two lists (digest ties) */
+    uint32_t n_pieces, digest_bits;
+    float stage_ms[KGX_UNIQ_STAGES]; /* summed over the pieces */
+} kgx_uniq_stats;
+int kgx_uniq_run(kgx_ctx *ctx, const char *residues, const uint64_t *seq_offsets, uint32_t n_seq,
+                 uint64_t piece_residues, uint32_t digest_bits, kgx_uniq **out);
+int kgx_uniq_stats_get(const kgx_uniq *u, kgx_uniq_stats *out);
+/* host views, valid until kgx_uniq_destroy: the groups as a CSR of sequence
+ * indices (group_offsets[n_groups + 1]; indices ascend within a group); each
+ * sequence's group; each group's ascending key list as a CSR in the same
+ * group order (set_offsets[n_groups + 1]) */
+int kgx_uniq_groups(const kgx_uniq *u, const uint64_t **group_offsets, const uint32_t **members, uint64_t *n_groups);
+int kgx_uniq_group_of(const kgx_uniq *u, const uint32_t **group, uint64_t *n_seq);
+int kgx_uniq_sets(const kgx_uniq *u, const uint64_t **set_offsets, const uint64_t **keys, uint64_t *n_groups);
+int kgx_uniq_destroy(kgx_uniq *u);
+
 /* ---- contexts: one per host thread, like one KmerGuts per pool thread --- */
 /* The environment variable KGX_PROBE_DEFER, read when a context is created,
  * picks the form of its line probe over a line index with marks: 1 or unset,
