@@ -198,6 +198,22 @@ class Fragments(ctypes.Structure):
                 ("n_bases", ctypes.c_uint64)]
 
 
+class FqText(ctypes.Structure):
+    """kgx_fq_text: the FASTA records of a batch of reads, on the device."""
+    _fields_ = [("n_reads", ctypes.c_uint32), ("n_fragments", ctypes.c_uint32), ("n_bytes", ctypes.c_uint64),
+                ("text", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("read", ctypes.c_void_p),
+                ("frame", ctypes.c_void_p), ("token", ctypes.c_void_p)]
+
+
+class F2pStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("reads", "reads_no_id", "fragments", "text_bytes", "parts")] + \
+        [("error_line", ctypes.c_uint32), ("gzip", ctypes.c_uint32)] + \
+        [(k, ctypes.c_double) for k in ("parse_ms", "upload_ms", "index_ms", "sizes_ms", "write_ms", "download_ms")]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def hits_from_packed(recs: np.ndarray) -> np.ndarray:
     """kgx_hit records (pos and seq 0) from HIT_PACKED16 records (uint32
     [n, 4]: the table's packed record, flags in bits 28-30 of word 3)."""
@@ -306,6 +322,12 @@ SIGNATURES = {
     "kgx_fq_fragments_device_start": (_INT, [_P, _P, _P, _U32, _U64]),
     "kgx_fq_fragments_finish": (_INT, [_P, ctypes.POINTER(Fragments)]),
     "kgx_fq_run_device": (_INT, [_P, ctypes.POINTER(Params), ctypes.POINTER(Fragments), _U32, _P]),
+    "kgx_fq_proteins": (_INT, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(FqText)]),
+    "kgx_f2p_create": (_INT, [_P, _U64, _PP]),
+    "kgx_f2p_destroy": (_INT, [_P]),
+    "kgx_f2p_process": (_INT, [_P, _CS, _U64, _INT, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_U64)]),
+    "kgx_f2p_get_stats": (_INT, [_P, ctypes.POINTER(F2pStats)]),
+    "kgx_f2p_error": (ctypes.c_char_p, [_P]),
     "kgx_fq_create": (_INT, [_P, _CS, _CS, _CS, _CS, _PP]),
     "kgx_fq_destroy": (_INT, [_P]),
     "kgx_fq_process": (_INT, [_P, _CS, _U64, _INT, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_U64)]),
@@ -846,6 +868,32 @@ class Context:
                 check(lib().kgx_memcpy_d2h(a.ctypes.data, ptr, a.nbytes), "d2h")
         return out
 
+    def fq_proteins(self, bases, read_offsets, ids, id_offsets) -> FqText:
+        """kgx_fq_proteins: the reads' six-frame FASTA records, left on the device."""
+        def u8(a):
+            return np.ascontiguousarray(np.frombuffer(bytes(a), np.uint8)
+                                        if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+        bases, ids = u8(bases), u8(ids)
+        off = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        ioff = np.ascontiguousarray(id_offsets, dtype=np.uint64)
+        if len(off) != len(ioff):
+            raise ValueError("read_offsets and id_offsets differ in length")
+        t = FqText()
+        check(lib().kgx_fq_proteins(self.handle, bases.ctypes.data if bases.size else None, off.ctypes.data,
+                                    ids.ctypes.data if ids.size else None, ioff.ctypes.data, len(off) - 1,
+                                    ctypes.byref(t)), "kgx_fq_proteins")
+        return t
+
+    def fq_text_to_host(self, t: FqText) -> dict:
+        """Host copies of a kgx_fq_text (tests / tools)."""
+        n = t.n_fragments
+        out = {"text": np.zeros(t.n_bytes, np.uint8), "offsets": np.zeros(n + 1 if t.offsets else 0, np.uint64),
+               "read": np.zeros(n, np.uint32), "frame": np.zeros(n, np.int8), "token": np.zeros(n, np.uint32)}
+        for k, a in out.items():
+            if a.nbytes:
+                check(lib().kgx_memcpy_d2h(a.ctypes.data, getattr(t, k), a.nbytes), "d2h")
+        return out
+
     def run_fragments(self, f: Fragments, params: Params | dict | None = None,
                       want: int = WANT_HITS | WANT_CALLS) -> BatchResult:
         """The lookup over device fragments, results collected to the host."""
@@ -1142,6 +1190,44 @@ class FqHandler:
     def close(self) -> None:
         if self.handle:
             lib().kgx_fq_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class FastqToProtein:
+    """fastq_to_protein as a streaming handle (kgx_f2p_*) on a context:
+    FASTQ text (plain or gzip) in blocks, the six-frame FASTA text out."""
+
+    def __init__(self, ctx: "Context", part_bytes: int = 0):
+        h = ctypes.c_void_p()
+        check(lib().kgx_f2p_create(ctx.handle, part_bytes, ctypes.byref(h)), "kgx_f2p_create")
+        self.handle = h.value
+        self.ctx = ctx  # the handle runs on it
+
+    def process(self, fastq: bytes, finished: bool = True) -> bytes:
+        t, n = ctypes.c_void_p(), ctypes.c_uint64()
+        fastq = bytes(fastq)  # passed by pointer, not copied
+        check(lib().kgx_f2p_process(self.handle, fastq, len(fastq), int(finished), ctypes.byref(t),
+                                    ctypes.byref(n)), "kgx_f2p_process")
+        return ctypes.string_at(t, n.value) if n.value else b""
+
+    def stats(self) -> dict:
+        st = F2pStats()
+        check(lib().kgx_f2p_get_stats(self.handle, ctypes.byref(st)), "kgx_f2p_get_stats")
+        return st.as_dict()
+
+    def error(self) -> str:
+        """The parse error of the file (the reference's report of it), "" if none."""
+        return (lib().kgx_f2p_error(self.handle) or b"").decode("latin-1")
+
+    def close(self) -> None:
+        if self.handle:
+            lib().kgx_f2p_destroy(self.handle)
             self.handle = None
 
     def __enter__(self):

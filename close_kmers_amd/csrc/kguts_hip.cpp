@@ -6,6 +6,7 @@
  * (fasta_parser.h:38-165, fasta_parser.cc:21-36).
  */
 #include "kguts_hip.h"
+#include "kgx_fq_parse.h" /* fq_parse: FastqParser::parse_char as the fq handler drives it */
 #include "kgx_score_map.h"
 
 #include <algorithm>
@@ -1899,95 +1900,6 @@ void FqRequest::process(const std::string &block, bool finished, std::ostream &o
 }
 
 namespace {
-
-enum { FQ_START, FQ_ID, FQ_DEF, FQ_DATA, FQ_PLUS_START, FQ_PLUS, FQ_QUAL };
-
-/* every byte a letter (isalpha in the C locale: A-Z, a-z): a branch-free
- * reduction the compiler vectorises */
-inline bool all_letters(const char *s, size_t n)
-{
-    unsigned bad = 0;
-    for (size_t i = 0; i < n; i++)
-        bad |= (unsigned)((unsigned char)((unsigned char)s[i] | 0x20u) - (unsigned char)'a') >= 26u;
-    return bad == 0;
-}
-
-inline bool is_letter(char c) { return (unsigned char)((unsigned char)c | 0x20u) - (unsigned char)'a' < 26u; }
-
-/* FastqParser::parse_char (fastq_parser.h:40-150), line-at-a-time, over
- * [p, end): the id runs to the first blank, sequence lines keep isalpha()
- * characters only (others are reported there and dropped), '+' and quality
- * lines are skipped; a record is emitted at the quality line's newline.  The
- * current record's residues are built in place at the end of `bases` (the
- * caller sizes it: at most one byte per byte parsed); `state` and `id` carry
- * the parser across calls. */
-void fq_parse(const char *p, const char *end, int &state, std::string &id, char *bases, size_t &n_bases,
-              std::vector<uint64_t> &roff, std::string &id_chars, std::vector<uint64_t> &id_off)
-{
-    size_t nb = n_bases;
-    while (p < end) {
-        switch (state) {
-        case FQ_START:
-            if (*p++ == '@')
-                state = FQ_ID;
-            break;
-        case FQ_ID: {
-            const char *q = p;
-            while (q < end && *q != ' ' && *q != '\t' && *q != '\n')
-                q++;
-            id.append(p, (size_t)(q - p));
-            if (q < end)
-                state = *q == '\n' ? FQ_DATA : FQ_DEF;
-            p = q < end ? q + 1 : end;
-            break;
-        }
-        case FQ_DEF:
-        case FQ_PLUS:
-        case FQ_QUAL: {
-            const char *nl = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
-            if (!nl) {
-                p = end;
-                break;
-            }
-            p = nl + 1;
-            if (state == FQ_QUAL) { /* emit */
-                id_chars += id;
-                id_off.push_back(id_chars.size());
-                roff.push_back(nb);
-                id.clear();
-                state = FQ_START;
-            } else {
-                state = state == FQ_DEF ? FQ_DATA : FQ_QUAL;
-            }
-            break;
-        }
-        case FQ_DATA: {
-            const char *nl = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
-            const char *stop = nl ? nl : end;
-            const size_t L = (size_t)(stop - p);
-            if (all_letters(p, L)) { /* the usual line: copied whole */
-                std::memcpy(bases + nb, p, L);
-                nb += L;
-            } else {
-                for (const char *q = p; q < stop; q++)
-                    if (is_letter(*q))
-                        bases[nb++] = *q;
-            }
-            p = stop;
-            if (nl) {
-                p = nl + 1;
-                state = FQ_PLUS_START;
-            }
-            break;
-        }
-        case FQ_PLUS_START:
-            if (*p++ == '+')
-                state = FQ_PLUS;
-            break;
-        }
-    }
-    n_bases = nb;
-}
 
 /* a place to cut a FASTQ block for a parallel parse: a line that starts
  * with '@' and whose next-but-one line starts with '+' (a record start in

@@ -1,0 +1,275 @@
+/*
+ * kgx_f2p.cpp -- fastq_to_protein as a streaming handle (include/kgx.h
+ * kgx_f2p_*): FASTQ text in blocks -> the strict parser
+ * (kgx_fq_parse.h) -> parts of at most part_bytes of text -> kgx_fq_proteins on
+ * the handle's context -> the part's text copied into pinned host memory.
+ * One context and one part at a time: a part's download does not overlap the
+ * next part's kernels.
+ */
+#include <chrono>
+
+#include "kgx_fq_parse.h"
+#include "kgx_rt.h"
+
+using namespace kgx;
+
+struct kgx_f2p {
+    kgx_ctx *ctx = nullptr;
+    uint64_t part_bytes = 0;
+    /* the body of the file being read: decided by its first bytes */
+    enum { BODY_UNKNOWN, BODY_HELD, BODY_TEXT, BODY_GZIP } body = BODY_UNKNOWN;
+    std::string gz_tail;     /* held first bytes / compressed bytes of an incomplete member */
+    uint64_t gz_members = 0; /* members inflated so far */
+    PinnedVec<char> gz_text; /* a block's inflated text */
+    /* the part being parsed */
+    FqStrict ps;
+    PinnedVec<char> bases;
+    size_t n_bases = 0;
+    std::vector<uint64_t> roff{0}, id_off{0};
+    std::string id_chars;
+    uint64_t part_taken = 0; /* FASTQ bytes parsed into it */
+    /* this call's text */
+    PinnedVec<char> out;
+    size_t out_len = 0;
+    std::vector<hipEvent_t> ev; /* download: start, end */
+    kgx_f2p_stats st{};
+    std::string err_text;
+    bool ended = true; /* the last call finished a file: the next one starts the stats anew */
+};
+
+namespace {
+
+/* the complete reads of the part through the device, their text appended to
+ * the call's output; the record in progress moves to the front */
+int flush_part(kgx_f2p *h)
+{
+    const uint32_t n = (uint32_t)(h->roff.size() - 1);
+    if (n) {
+        for (uint32_t r = 0; r < n; r++)
+            h->st.reads_no_id += h->id_off[r + 1] == h->id_off[r];
+        kgx_fq_text t;
+        if (int rc = fq_proteins(h->ctx, h->bases.data(), h->roff.data(), h->id_chars.data(), h->id_off.data(), n, &t))
+            return rc;
+        hipStream_t s = h->ctx->stream;
+        if (t.n_bytes) {
+            HIP_TRY(h->out.resize(h->out_len + t.n_bytes));
+            HIP_TRY(hipEventRecord(h->ev[0], s));
+            HIP_TRY(hipMemcpyAsync(h->out.data() + h->out_len, t.text, t.n_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(h->ev[1], s));
+            HIP_TRY(host_wait(s));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            h->st.download_ms += ms;
+            h->out_len += t.n_bytes;
+        }
+        const float *ms = h->ctx->ft_ms;
+        h->st.upload_ms += ms[0];
+        h->st.index_ms += ms[1];
+        h->st.sizes_ms += ms[2];
+        h->st.write_ms += ms[3];
+        h->st.reads += n;
+        h->st.fragments += t.n_fragments;
+        h->st.text_bytes += t.n_bytes;
+        h->st.parts++;
+    }
+    const size_t done = (size_t)h->roff.back();
+    if (h->n_bases > done)
+        std::memmove(h->bases.data(), h->bases.data() + done, h->n_bases - done);
+    h->n_bases -= done;
+    h->roff.assign(1, 0);
+    h->id_off.assign(1, 0);
+    h->id_chars.clear();
+    h->part_taken = 0;
+    return KGX_OK;
+}
+
+int process_text(kgx_f2p *h, const char *text, size_t n, bool finished)
+{
+    size_t pos = 0;
+    while (pos < n && !h->ps.stopped) {
+        const size_t take = (size_t)std::min<uint64_t>(n - pos, h->part_bytes - h->part_taken);
+        HIP_TRY(h->bases.resize(h->n_bases + take + 16));
+        const auto t0 = std::chrono::steady_clock::now();
+        fq_parse_strict(text + pos, text + pos + take, h->ps, h->bases.data(), h->n_bases, h->roff, h->id_chars,
+                        h->id_off);
+        h->st.parse_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pos += take;
+        h->part_taken += take;
+        if (h->part_taken >= h->part_bytes || h->ps.stopped)
+            if (int rc = flush_part(h))
+                return rc;
+    }
+    if (finished) {
+        /* the bases of a record in progress without an id go with it */
+        if (h->ps.stopped || h->ps.id.empty())
+            h->n_bases = (size_t)h->roff.back();
+        fq_parse_strict_finish(h->ps, h->n_bases, h->roff, h->id_chars, h->id_off);
+        if (int rc = flush_part(h))
+            return rc;
+    }
+    if (h->ps.err_line && !h->st.error_line) {
+        h->st.error_line = h->ps.err_line;
+        h->err_text = h->ps.message();
+    }
+    return KGX_OK;
+}
+
+/* the block's complete gzip members -> text -> process_text (FqRequest::process_gzip) */
+int process_gzip(kgx_f2p *h, const char *block, size_t n, bool finished)
+{
+    if (h->ps.stopped) /* after a parse error nothing more is read */
+        return KGX_OK;
+    h->gz_tail.append(block, n);
+    /* trailing bytes after a member that are no gzip are ignored, as gzip does */
+    if (h->gz_members && h->gz_tail.size() >= 2 &&
+        !((unsigned char)h->gz_tail[0] == 0x1f && (unsigned char)h->gz_tail[1] == 0x8b))
+        h->gz_tail.clear();
+    uint64_t members = 0, blocked = 0, out_bytes = 0, consumed = 0, out_len = 0;
+    if (int rc = kgx_gunzip_scan(h->gz_tail.data(), h->gz_tail.size(), finished, &members, &blocked, &out_bytes,
+                                 &consumed))
+        return rc;
+    /* blocked members state their sizes; a plain member's is found by trying */
+    size_t cap = (size_t)out_bytes + 64;
+    if (members > blocked && finished)
+        cap += 6 * h->gz_tail.size() + (size_t(1) << 20);
+    for (;;) {
+        h->gz_text.n = 0; /* nothing to keep when it grows */
+        HIP_TRY(h->gz_text.resize(cap));
+        kgx_gunzip_stats gs;
+        const int rc = kgx_gunzip(h->ctx, h->gz_tail.data(), h->gz_tail.size(), finished, h->gz_text.data(), cap,
+                                  &out_len, &consumed, &gs);
+        if (rc == KGX_ERANGE && members > blocked) {
+            cap *= 2;
+            continue;
+        }
+        if (rc)
+            return rc;
+        h->gz_members += gs.members;
+        break;
+    }
+    h->gz_tail.erase(0, (size_t)consumed);
+    return process_text(h, h->gz_text.data(), (size_t)out_len, finished);
+}
+
+/* the file ends, in its last block or in an error: the next call starts one */
+void end_file(kgx_f2p *h)
+{
+    h->body = kgx_f2p::BODY_UNKNOWN;
+    h->gz_tail.clear();
+    h->gz_members = 0;
+    h->ps.reset();
+    h->n_bases = 0;
+    h->roff.assign(1, 0);
+    h->id_off.assign(1, 0);
+    h->id_chars.clear();
+    h->part_taken = 0;
+    h->ended = true;
+}
+
+/* the sniff at the start of a file, as FqRequest::process: 1f 8b 08 makes the
+ * whole file gzip; a first block shorter than gzip's fixed header that begins
+ * with 1f is held until more arrives or the file ends */
+int process_block(kgx_f2p *h, const char *block, size_t n, bool finished)
+{
+    if (h->body == kgx_f2p::BODY_UNKNOWN || h->body == kgx_f2p::BODY_HELD) {
+        const std::string &held = h->gz_tail;
+        auto byte = [&](size_t i) { return (unsigned char)(i < held.size() ? held[i] : block[i - held.size()]); };
+        const size_t have = held.size() + n;
+        if (have == 0 || byte(0) != 0x1f)
+            h->body = kgx_f2p::BODY_TEXT;
+        else if (have >= 3)
+            h->body = byte(1) == 0x8b && byte(2) == 8 ? kgx_f2p::BODY_GZIP : kgx_f2p::BODY_TEXT;
+        else if (finished)
+            h->body = kgx_f2p::BODY_TEXT;
+        else
+            h->body = kgx_f2p::BODY_HELD;
+        if (h->body == kgx_f2p::BODY_GZIP && have < 10 && !finished)
+            h->body = kgx_f2p::BODY_HELD;
+        if (h->body == kgx_f2p::BODY_HELD) {
+            h->gz_tail.append(block, n);
+            return KGX_OK;
+        }
+        if (h->body == kgx_f2p::BODY_TEXT && !h->gz_tail.empty()) { /* held bytes that were text after all */
+            std::string all;
+            all.swap(h->gz_tail);
+            all.append(block, n);
+            return process_text(h, all.data(), all.size(), finished);
+        }
+    }
+    if (h->body == kgx_f2p::BODY_GZIP) {
+        h->st.gzip = 1;
+        return process_gzip(h, block, n, finished);
+    }
+    return process_text(h, block, n, finished);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgx_f2p_create(kgx_ctx *ctx, uint64_t part_bytes, kgx_f2p **out)
+{
+    if (!ctx || !out)
+        return fail(KGX_EINVAL, "null argument");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(ctx->img->device));
+    std::unique_ptr<kgx_f2p> h(new kgx_f2p);
+    h->ctx = ctx;
+    h->part_bytes = part_bytes ? part_bytes : uint64_t(32) << 20;
+    if (int rc = ensure_events(h->ev, 2, hipEventDefault))
+        return rc;
+    *out = h.release();
+    return KGX_OK;
+}
+
+int kgx_f2p_destroy(kgx_f2p *h)
+{
+    if (h)
+        for (hipEvent_t e : h->ev)
+            (void)hipEventDestroy(e);
+    delete h;
+    return KGX_OK;
+}
+
+int kgx_f2p_process(kgx_f2p *h, const char *fastq, uint64_t n, int finished, const char **text, uint64_t *text_len)
+{
+    if (!h || (n && !fastq) || !text || !text_len)
+        return fail(KGX_EINVAL, "null argument");
+    *text = "";
+    *text_len = 0;
+    HIP_TRY(hipSetDevice(h->ctx->img->device));
+    if (h->ended) {
+        h->st = kgx_f2p_stats{};
+        h->err_text.clear();
+        h->ended = false;
+    }
+    h->out.n = 0; /* the last call's text is not kept when the buffer grows */
+    h->out_len = 0;
+    int rc;
+    try {
+        rc = process_block(h, fastq ? fastq : "", (size_t)n, finished != 0);
+    } catch (const std::exception &e) {
+        rc = fail(KGX_ENOMEM, e.what());
+    }
+    if (rc || finished)
+        end_file(h);
+    if (rc)
+        return rc;
+    if (h->out_len) {
+        *text = h->out.data();
+        *text_len = h->out_len;
+    }
+    return KGX_OK;
+}
+
+int kgx_f2p_get_stats(const kgx_f2p *h, kgx_f2p_stats *out)
+{
+    if (!h || !out)
+        return fail(KGX_EINVAL, "null argument");
+    *out = h->st;
+    return KGX_OK;
+}
+
+const char *kgx_f2p_error(const kgx_f2p *h) { return h ? h->err_text.c_str() : ""; }
+
+}  // extern "C"

@@ -370,7 +370,8 @@ constexpr uint64_t EVERY3 = 0x9249249249249249ull; /* bits 0, 3, ..., 63 */
 
 /* the runs of frame f ending at the stops in m (bit i = a stop ending at base
  * base + i): v(f, prev, q, L) for each kept run of L codons between the stops
- * ending at prev and q */
+ * ending at prev and q; a visitor with every_stop also gets v.stop(f, L) for
+ * every stop, kept run or not (the token numbering of kgx_fq_proteins) */
 template <class V>
 __device__ __forceinline__ void frame_runs(uint64_t m, int base, uint32_t f, int &prev, V &v)
 {
@@ -380,6 +381,8 @@ __device__ __forceinline__ void frame_runs(uint64_t m, int base, uint32_t f, int
         const int L = (q - prev) / 3 - 1;
         if (L >= (int)MIN_FRAGMENT)
             v(f, prev, q, L);
+        if constexpr (V::every_stop)
+            v.stop(f, L);
         prev = q;
     }
 }
@@ -411,6 +414,7 @@ struct RunCount {
         nf++;
         nr += (uint32_t)L;
     }
+    static constexpr bool every_stop = false;
 };
 
 /* a read's kept runs straight from its bytes in memory, one base at a time:
@@ -573,6 +577,7 @@ struct RunCount6 {
         nf[f]++;
         nr[f] += (uint32_t)L;
     }
+    static constexpr bool every_stop = false;
 };
 
 /* FRAMES (the anchors' pass): also each frame's fragments and residues,
@@ -663,6 +668,7 @@ struct RunWrite {
         out_off[idx] = ro;
         out_anchor[idx] = anchor;
     }
+    static constexpr bool every_stop = false;
 };
 
 /*
@@ -1456,6 +1462,486 @@ int kgx_fq_fragments(kgx_ctx *c, const char *bases, const uint64_t *read_offsets
         return fail(KGX_EINVAL, "null argument");
     const int rc = kgx_fq_upload(c, bases, read_offsets, n_reads);
     return rc ? rc : kgx_fq_fragments_uploaded(c, out);
+}
+
+}  // extern "C"
+
+/* ---- reads -> six-frame protein FASTA (kgx_fq_proteins) ----
+ *
+ * fastq_to_protein.cc:24-47 writes, per read with an id and per frame, every
+ * token of the translation split at '*' that is longer than 10 residues as
+ * ">ID:FRAME:INDEX\nTOKEN\n", INDEX counting all the frame's tokens from 1.
+ * The kept tokens are the fragments of the passes above; what is new is INDEX
+ * and the text.
+ *
+ * INDEX from the stops (frame_runs): the first token always exists; a stop
+ * opens the next token when at least one codon lies between it and the stop
+ * before it, or when it is the frame's first stop (a separator at the very
+ * start still leaves an empty token before it; a run of adjacent stops is one
+ * separator).  The scan walks the forward strand, so it meets a reverse
+ * frame's tokens last to first: there the same count, taken in scan order, is
+ * subtracted from the frame's total T: INDEX = T + 1 - (scan-order index).
+ *
+ * Launches: count (a lane per read: fragments per read and frame, T per frame)
+ * -> scan of the reads' fragment counts (hipcub) -> index (the same scan
+ * again: per fragment its anchor, length, INDEX, read, frame and record size)
+ * -> scan of the sizes into 64-bit record offsets (hipcub) -> write.  The host
+ * reads the fragment total after the first scan and the byte total after the
+ * second, to size the buffers.
+ *
+ * The writer: a workgroup owns 4096 contiguous bytes of text, finds the
+ * records that overlap them by searching the offsets, keeps their fields in
+ * LDS, and every lane produces one aligned 16-byte store: header bytes from
+ * the id and the numbers, residues translated from the bases at the anchor
+ * (complemented on the reverse strand) with kCode11.  No residue is
+ * materialised in between.
+ */
+namespace {
+
+/* per frame: kept fragments and tokens so far (all of them at the end) */
+struct TokenCount6 {
+    static constexpr bool every_stop = true;
+    uint32_t nf[6] = {0, 0, 0, 0, 0, 0}, tok[6] = {1, 1, 1, 1, 1, 1};
+    uint32_t seen = 0; /* bit f: frame f has met a stop */
+    __device__ __forceinline__ void operator()(uint32_t f, int, int, int) { nf[f]++; }
+    __device__ __forceinline__ void stop(uint32_t f, int L)
+    {
+        tok[f] += (L >= 1 || !((seen >> f) & 1u)) ? 1u : 0u;
+        seen |= 1u << f;
+    }
+};
+
+__device__ __forceinline__ uint32_t dec_digits(uint32_t v)
+{
+    uint32_t n = 1;
+    for (uint32_t p = 10; n < 10 && v >= p; p *= 10)
+        n++;
+    return n;
+}
+
+/* bytes of ">ID:FRAME:INDEX\n" */
+__device__ __forceinline__ uint32_t header_bytes(uint32_t id_len, uint32_t f, uint32_t token)
+{
+    return 1 + id_len + 1 + (f < 3 ? 1u : 2u) + 1 + dec_digits(token) + 1;
+}
+
+/* the fragments' records in (frame, position) order, as RunWrite places them */
+struct TokenWrite {
+    static constexpr bool every_stop = true;
+    uint64_t fi[6]; /* next fragment slot (forward) / last unwritten (reverse) */
+    uint32_t tok[6] = {1, 1, 1, 1, 1, 1}, total[6];
+    uint32_t seen = 0;
+    uint64_t ob;
+    uint32_t r, id_len;
+    uint64_t *anchor;
+    uint32_t *len, *token, *read, *size;
+    int8_t *frame;
+    __device__ __forceinline__ void operator()(uint32_t f, int prev, int q, int L)
+    {
+        uint64_t idx, a;
+        uint32_t t;
+        if (f < 3) {
+            idx = fi[f]++;
+            a = (ob + (uint64_t)(prev + 1)) << 1;
+            t = tok[f];
+        } else {
+            idx = fi[f]--;
+            a = ((ob + (uint64_t)(q - 3)) << 1) | 1u;
+            t = total[f] + 1 - tok[f];
+        }
+        anchor[idx] = a;
+        len[idx] = (uint32_t)L;
+        token[idx] = t;
+        read[idx] = r;
+        frame[idx] = (int8_t)frame_of(f);
+        size[idx] = header_bytes(id_len, f, t) + (uint32_t)L + 1;
+    }
+    __device__ __forceinline__ void stop(uint32_t f, int L)
+    {
+        tok[f] += (L >= 1 || !((seen >> f) & 1u)) ? 1u : 0u;
+        seen |= 1u << f;
+    }
+};
+
+/* 1. per (read, frame): fragments and tokens; per read: fragments (0 for a
+ * read without an id); read_cnt[n_reads] = 0, the scan's tail */
+__global__ __launch_bounds__(256) void fq_text_count_kernel(const uint8_t *bases, const uint64_t *read_off,
+                                                            const uint64_t *id_off, uint32_t n_reads, uint32_t n_tiles,
+                                                            uint32_t *frame_nf, uint32_t *frame_tok, uint64_t *read_cnt)
+{
+    __shared__ uint32_t nspan[WAVES_PER_WG][NS_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t tile = blockIdx.x * WAVES_PER_WG + wv;
+    if (tile >= n_tiles)
+        return;
+    uint32_t *ns = nspan[wv];
+    const uint64_t r0 = (uint64_t)tile * FQ_TILE;
+    const uint32_t n = (uint32_t)std::min<uint64_t>(FQ_TILE, n_reads - r0);
+    const uint64_t r = r0 + lane;
+    const uint64_t ob = lane < n ? read_off[r] : 0, oe = lane < n ? read_off[r + 1] : 0;
+    const bool named = lane < n && id_off[r + 1] > id_off[r];
+    const uint64_t first = uniform_u64(__shfl(ob, 0)), end = uniform_u64(__shfl(oe, (int)n - 1));
+    uintptr_t a = 0;
+    const bool staged = stage_span(ns, bases, first, end, lane, a);
+    if (lane >= n)
+        return;
+    TokenCount6 tc;
+    if (named) {
+        if (staged)
+            lane_read_runs_ns(ns, (uint32_t)(reinterpret_cast<uintptr_t>(bases + ob) - a), (uint32_t)(oe - ob), tc);
+        else
+            lane_read_runs_global(bases + ob, (uint32_t)(oe - ob), tc);
+    }
+    uint32_t nf = 0;
+#pragma unroll
+    for (uint32_t f = 0; f < 6; f++) {
+        frame_nf[r * 6 + f] = named ? tc.nf[f] : 0u;
+        frame_tok[r * 6 + f] = tc.tok[f];
+        nf += named ? tc.nf[f] : 0u;
+    }
+    read_cnt[r] = nf;
+    if (r == (uint64_t)n_reads - 1)
+        read_cnt[n_reads] = 0;
+}
+
+/* 3. per fragment: anchor, length, token index, read, frame and record size,
+ * at read_base[r] + the earlier frames' fragments; size[total] = 0 */
+__global__ __launch_bounds__(256) void fq_text_index_kernel(const uint8_t *bases, const uint64_t *read_off,
+                                                            const uint64_t *id_off, uint32_t n_reads, uint32_t n_tiles,
+                                                            const uint32_t *frame_nf, const uint32_t *frame_tok,
+                                                            const uint64_t *read_base, uint64_t *anchor, uint32_t *len,
+                                                            uint32_t *token, uint32_t *read, int8_t *frame,
+                                                            uint32_t *size)
+{
+    __shared__ uint32_t nspan[WAVES_PER_WG][NS_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t tile = blockIdx.x * WAVES_PER_WG + wv;
+    if (tile >= n_tiles)
+        return;
+    uint32_t *ns = nspan[wv];
+    const uint64_t r0 = (uint64_t)tile * FQ_TILE;
+    const uint32_t n = (uint32_t)std::min<uint64_t>(FQ_TILE, n_reads - r0);
+    const uint64_t r = r0 + lane;
+    const uint64_t ob = lane < n ? read_off[r] : 0, oe = lane < n ? read_off[r + 1] : 0;
+    const uint64_t ib = lane < n ? id_off[r] : 0, ie = lane < n ? id_off[r + 1] : 0;
+    const uint64_t first = uniform_u64(__shfl(ob, 0)), end = uniform_u64(__shfl(oe, (int)n - 1));
+    uintptr_t a = 0;
+    const bool staged = stage_span(ns, bases, first, end, lane, a);
+    if (lane >= n)
+        return;
+    if (r == (uint64_t)n_reads - 1)
+        size[read_base[n_reads]] = 0;
+    if (ie == ib) /* no id: no records */
+        return;
+    TokenWrite w;
+    uint64_t fb = read_base[r];
+#pragma unroll
+    for (uint32_t f = 0; f < 6; f++) {
+        const uint32_t nf = frame_nf[r * 6 + f];
+        w.fi[f] = f < 3 ? fb : fb + nf - 1;
+        w.total[f] = frame_tok[r * 6 + f];
+        fb += nf;
+    }
+    w.ob = ob;
+    w.r = (uint32_t)r;
+    w.id_len = (uint32_t)(ie - ib);
+    w.anchor = anchor;
+    w.len = len;
+    w.token = token;
+    w.read = read;
+    w.frame = frame;
+    w.size = size;
+    if (staged)
+        lane_read_runs_ns(ns, (uint32_t)(reinterpret_cast<uintptr_t>(bases + ob) - a), (uint32_t)(oe - ob), w);
+    else
+        lane_read_runs_global(bases + ob, (uint32_t)(oe - ob), w);
+}
+
+constexpr uint32_t TEXT_SPAN = 4096;  /* bytes of text per workgroup: 256 lanes x 16 */
+constexpr uint32_t TEXT_MIN_RECORD = 19; /* ">i:1:1\n" + 11 residues + "\n" */
+constexpr uint32_t TEXT_RECS = 224;   /* records that can overlap a span, and one past them */
+static_assert(TEXT_SPAN / TEXT_MIN_RECORD + 3 <= TEXT_RECS, "a span's records fit the LDS arrays");
+
+struct TextLds {
+    char code[68];
+    uint32_t g0, nrec;
+    int32_t rel[TEXT_RECS]; /* record start - span start (the first <= 0; past the last: a sentinel) */
+    uint64_t anchor[TEXT_RECS], id_at[TEXT_RECS];
+    uint32_t len[TEXT_RECS], hdr[TEXT_RECS], id_len[TEXT_RECS], token[TEXT_RECS];
+    int32_t frame[TEXT_RECS];
+};
+
+/* the largest g in [0, n) with off[g] <= x (off ascending, off[0] <= x): the
+ * wave probes 64 evenly spaced offsets a step */
+__device__ __forceinline__ uint64_t wave_last_le(const uint64_t *off, uint64_t n, uint64_t x, uint32_t lane)
+{
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint64_t step = (hi - lo + 63) / 64;
+        const uint64_t idx = lo + (uint64_t)(lane + 1) * step;
+        /* every lane loads (an index past hi re-reads lo); the test selects */
+        const uint64_t v = off[idx < hi ? idx : lo];
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(idx < hi && v <= x));
+        const uint64_t nlo = lo + (uint64_t)cnt * step;
+        hi = std::min<uint64_t>(hi, nlo + step);
+        lo = nlo;
+    }
+    return uniform_u64(lo);
+}
+
+/* residue k of the fragment at anchor a (FrameReader::aa from an anchor) */
+__device__ __forceinline__ char anchor_aa(const uint8_t *bases, const char *code, uint64_t a, uint32_t k)
+{
+    const uint8_t *b = bases + (a >> 1);
+    uint32_t e1, e2, e3;
+    if (a & 1) {
+        b -= 3 * (uint64_t)k;
+        e1 = base_class(b[0]);
+        e2 = base_class(b[-1]);
+        e3 = base_class(b[-2]);
+        if (e1 < 4 && e2 < 4 && e3 < 4)
+            return code[63u - (e1 * 16 + e2 * 4 + e3)]; /* the complement of every base */
+        return code[64];
+    }
+    b += 3 * (uint64_t)k;
+    e1 = base_class(b[0]);
+    e2 = base_class(b[1]);
+    e3 = base_class(b[2]);
+    return (e1 < 4 && e2 < 4 && e3 < 4) ? code[e1 * 16 + e2 * 4 + e3] : code[64];
+}
+
+/* 5. the text.  n_frag >= 1; grid = ceil(n_bytes / TEXT_SPAN); the buffer
+ * holds whole spans, the bytes past n_bytes are written as 0 */
+__global__ __launch_bounds__(256) void fq_text_write_kernel(const uint8_t *bases, const uint8_t *ids,
+                                                            const uint64_t *id_off, const uint64_t *off,
+                                                            const uint64_t *anchor, const uint32_t *len,
+                                                            const uint32_t *token, const uint32_t *read,
+                                                            const int8_t *frame, uint32_t n_frag, uint64_t n_bytes,
+                                                            uint8_t *text)
+{
+    __shared__ TextLds t;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint64_t s0 = (uint64_t)blockIdx.x * TEXT_SPAN;
+    if (tid < 65)
+        t.code[tid] = kCode11[tid];
+    if (tid < 64) {
+        /* the records [g0, g1] overlap [s0, min(s0 + span, n_bytes)) */
+        const uint64_t last = std::min<uint64_t>(s0 + TEXT_SPAN, n_bytes) - 1;
+        const uint64_t g0 = wave_last_le(off, n_frag, s0, lane);
+        const uint64_t g1 = wave_last_le(off, n_frag, last, lane);
+        if (lane == 0) {
+            t.g0 = (uint32_t)g0;
+            t.nrec = (uint32_t)std::min<uint64_t>(g1 - g0 + 1, TEXT_RECS - 1);
+        }
+    }
+    __syncthreads();
+    const uint32_t g0 = t.g0, nrec = t.nrec;
+    if (tid <= nrec) {
+        const uint64_t g = (uint64_t)g0 + tid;
+        const int64_t d = (int64_t)(off[g] - s0); /* off[n_frag] = n_bytes */
+        t.rel[tid] = (int32_t)std::min<int64_t>(std::max<int64_t>(d, INT32_MIN), INT32_MAX);
+        if (tid < nrec) {
+            const uint32_t r = read[g], tk = token[g];
+            const int32_t fr = frame[g];
+            const uint64_t ib = id_off[r];
+            const uint32_t il = (uint32_t)(id_off[r + 1] - ib);
+            t.anchor[tid] = anchor[g];
+            t.len[tid] = len[g];
+            t.token[tid] = tk;
+            t.frame[tid] = fr;
+            t.id_at[tid] = ib;
+            t.id_len[tid] = il;
+            t.hdr[tid] = header_bytes(il, fr > 0 ? 0u : 3u, tk);
+        }
+    }
+    __syncthreads();
+    const int32_t p = (int32_t)(tid * 16);
+    if (s0 + (uint64_t)p >= n_bytes)
+        return;
+    /* the record holding byte p: the last slot with rel <= p */
+    uint32_t lo = 0, hi = nrec;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (t.rel[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t i = lo;
+    uint32_t j = (uint32_t)(p - t.rel[i]);
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t b = 0; b < 16; b++) {
+        uint32_t ch = 0;
+        if (i < nrec) {
+            const uint32_t hdr = t.hdr[i], L = t.len[i];
+            if (j >= hdr) {
+                ch = j - hdr < L ? (uint32_t)(uint8_t)anchor_aa(bases, t.code, t.anchor[i], j - hdr) : (uint32_t)'\n';
+            } else {
+                const uint32_t il = t.id_len[i];
+                const int32_t fr = t.frame[i];
+                if (j == 0) {
+                    ch = '>';
+                } else if (j <= il) {
+                    ch = ids[t.id_at[i] + (j - 1)];
+                } else {
+                    /* ":FRAME:INDEX\n", u bytes from its end */
+                    const uint32_t u = hdr - 1 - j;
+                    const uint32_t nd = hdr - il - (fr > 0 ? 5u : 6u);
+                    if (u == 0) {
+                        ch = '\n';
+                    } else if (u <= nd) {
+                        uint32_t v = t.token[i];
+                        for (uint32_t k = 1; k < u; k++)
+                            v /= 10;
+                        ch = '0' + v % 10;
+                    } else if (u == nd + 1 || j == il + 1) {
+                        ch = ':';
+                    } else if (fr < 0 && j == il + 2) {
+                        ch = '-';
+                    } else {
+                        ch = '0' + (uint32_t)(fr < 0 ? -fr : fr);
+                    }
+                }
+            }
+            j++;
+            if (j == hdr + L + 1) {
+                i++;
+                j = 0;
+            }
+        }
+        w[b >> 2] |= ch << (8 * (b & 3));
+    }
+    *reinterpret_cast<uint4 *>(text + s0 + (uint64_t)p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+struct WidenU32 {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
+};
+
+}  // namespace
+
+namespace kgx {
+
+/* reads and ids in host memory -> the records on the device (see above) */
+int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
+                const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out)
+{
+    hipStream_t st = c->stream;
+    if (int rc = ensure_events(c->ft_events, 5, hipEventDefault))
+        return rc;
+    for (float &m : c->ft_ms)
+        m = 0;
+    *out = kgx_fq_text{};
+    out->n_reads = n_reads;
+    c->fq_pend.active = false;
+    if (!n_reads)
+        return KGX_OK;
+    const uint64_t i0 = id_offsets[0], n_id = id_offsets[n_reads] - i0;
+    if (n_id && !ids)
+        return fail(KGX_EINVAL, "null ids");
+    HIP_TRY(c->h_ft_idoff.resize((uint64_t)n_reads + 1));
+    for (uint32_t r = 0; r <= n_reads; r++) {
+        if (r && id_offsets[r] < id_offsets[r - 1])
+            return fail(KGX_EINVAL, "id_offsets not monotone");
+        c->h_ft_idoff[r] = id_offsets[r] - i0;
+    }
+    HIP_TRY(hipEventRecord(c->ft_events[0], st));
+    if (int rc = kgx_fq_upload(c, bases, read_offsets, n_reads))
+        return rc;
+    c->fq_up.active = false;
+    const uint64_t n_bases = c->fq_up.n_bases;
+    HIP_TRY(c->ft_ids.reserve(n_id + 16));
+    HIP_TRY(c->ft_idoff.reserve(((uint64_t)n_reads + 1) * 8));
+    HIP_TRY(hipMemcpyAsync(c->ft_idoff.p, c->h_ft_idoff.data(), ((uint64_t)n_reads + 1) * 8, hipMemcpyHostToDevice,
+                           st));
+    if (n_id)
+        HIP_TRY(hipMemcpyAsync(c->ft_ids.p, ids + i0, n_id, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(c->ft_events[1], st));
+
+    const uint64_t n_rf = (uint64_t)n_reads * 6;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n_reads + FQ_TILE - 1) / FQ_TILE);
+    const dim3 grid((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG);
+    HIP_TRY(c->fq_nfrag.reserve((n_rf + 1) * 4));
+    HIP_TRY(c->ft_tok6.reserve((n_rf + 1) * 4));
+    HIP_TRY(c->ft_rcnt.reserve(((uint64_t)n_reads + 1) * 8));
+    HIP_TRY(c->ft_rbase.reserve(((uint64_t)n_reads + 1) * 8));
+    HIP_TRY(c->h_fq_tot.resize(2));
+    const uint8_t *d_bases = c->fq_bases.as<uint8_t>();
+    const uint64_t *d_roff = c->fq_roff.as<uint64_t>(), *d_ioff = c->ft_idoff.as<uint64_t>();
+    hipLaunchKernelGGL(fq_text_count_kernel, grid, dim3(256), 0, st, d_bases, d_roff, d_ioff, n_reads, n_tiles,
+                       c->fq_nfrag.as<uint32_t>(), c->ft_tok6.as<uint32_t>(), c->ft_rcnt.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c->ft_rcnt.as<uint64_t>(), c->ft_rbase.as<uint64_t>(),
+                                             (int)(n_reads + 1), st));
+    HIP_TRY(c->fq_tmp.reserve(tb));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->fq_tmp.p, tb, c->ft_rcnt.as<uint64_t>(), c->ft_rbase.as<uint64_t>(),
+                                             (int)(n_reads + 1), st));
+    HIP_TRY(hipMemcpyAsync(c->h_fq_tot.data(), c->ft_rbase.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(host_wait(st));
+    const uint64_t nf = c->h_fq_tot[0];
+    /* six frames give at most 2 residues per base, a fragment has at least 11 */
+    if (nf > 2 * n_bases / MIN_FRAGMENT + 1)
+        return fail(KGX_EDEVICE, "kgx_fq_proteins: more fragments than the bases allow");
+    if (nf >= (1ull << 31))
+        return fail(KGX_ERANGE, "kgx_fq_proteins: 2^31 fragments or more in one call");
+    HIP_TRY(c->ft_anchor.reserve((nf + 1) * 8));
+    HIP_TRY(c->ft_len.reserve((nf + 1) * 4));
+    HIP_TRY(c->ft_token.reserve((nf + 1) * 4));
+    HIP_TRY(c->ft_read.reserve((nf + 1) * 4));
+    HIP_TRY(c->ft_frame.reserve(nf + 1));
+    HIP_TRY(c->ft_size.reserve((nf + 1) * 4));
+    HIP_TRY(c->ft_off.reserve((nf + 1) * 8));
+    hipLaunchKernelGGL(fq_text_index_kernel, grid, dim3(256), 0, st, d_bases, d_roff, d_ioff, n_reads, n_tiles,
+                       c->fq_nfrag.as<uint32_t>(), c->ft_tok6.as<uint32_t>(), c->ft_rbase.as<uint64_t>(),
+                       c->ft_anchor.as<uint64_t>(), c->ft_len.as<uint32_t>(), c->ft_token.as<uint32_t>(),
+                       c->ft_read.as<uint32_t>(), c->ft_frame.as<int8_t>(), c->ft_size.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ft_events[2], st));
+    hipcub::TransformInputIterator<uint64_t, WidenU32, const uint32_t *> sizes(c->ft_size.as<uint32_t>(), WidenU32());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sizes, c->ft_off.as<uint64_t>(), (int)(nf + 1), st));
+    HIP_TRY(c->fq_tmp.reserve(tb));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->fq_tmp.p, tb, sizes, c->ft_off.as<uint64_t>(), (int)(nf + 1), st));
+    HIP_TRY(hipMemcpyAsync(c->h_fq_tot.data() + 1, c->ft_off.as<uint64_t>() + nf, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(c->ft_events[3], st));
+    HIP_TRY(host_wait(st));
+    const uint64_t nb = c->h_fq_tot[1];
+    const uint64_t spans = (nb + TEXT_SPAN - 1) / TEXT_SPAN;
+    if (spans >= (1ull << 31))
+        return fail(KGX_ERANGE, "kgx_fq_proteins: 8 TB of text or more in one call");
+    HIP_TRY(c->ft_text.reserve(spans * TEXT_SPAN + 16));
+    if (nf)
+        hipLaunchKernelGGL(fq_text_write_kernel, dim3((uint32_t)spans), dim3(256), 0, st, d_bases,
+                           c->ft_ids.as<uint8_t>(), d_ioff, c->ft_off.as<uint64_t>(), c->ft_anchor.as<uint64_t>(),
+                           c->ft_len.as<uint32_t>(), c->ft_token.as<uint32_t>(), c->ft_read.as<uint32_t>(),
+                           c->ft_frame.as<int8_t>(), (uint32_t)nf, nb, c->ft_text.as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ft_events[4], st));
+    HIP_TRY(host_wait(st));
+    for (int i = 0; i < 4; i++)
+        HIP_TRY(hipEventElapsedTime(&c->ft_ms[i], c->ft_events[i], c->ft_events[i + 1]));
+    out->n_fragments = (uint32_t)nf;
+    out->n_bytes = nb;
+    out->text = c->ft_text.as<char>();
+    out->offsets = c->ft_off.as<uint64_t>();
+    out->read = c->ft_read.as<uint32_t>();
+    out->frame = c->ft_frame.as<int8_t>();
+    out->token = c->ft_token.as<uint32_t>();
+    return KGX_OK;
+}
+
+}  // namespace kgx
+
+extern "C" {
+
+int kgx_fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
+                    const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out)
+{
+    if (!c || !out || (n_reads && (!read_offsets || !id_offsets)))
+        return fail(KGX_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->img->device));
+    return fq_proteins(c, bases, read_offsets, ids, id_offsets, n_reads, out);
 }
 
 }  // extern "C"

@@ -11,6 +11,9 @@
  *   add            add_request.cc:305-353 (silent=0)
  *   fq             the input is FASTQ: fq_process_request.cc:230-365 over
  *                  FamilyMapper; genus=, families=, nr= load the family DB
+ *   proteins       the input is FASTQ (plain or gzip): fastq_to_protein.cc, every
+ *                  six-frame fragment longer than 10 residues as a FASTA
+ *                  record >ID:FRAME:INDEX (kgx_f2p_*)
  *   lookup         /lookup (lookup_request.cc:153-400): family_mode=1 loads
  *                  the family DB (genus=, families=, nr=); otherwise the FASTA
  *                  is first /add-ed into kmer_to_id_
@@ -40,7 +43,7 @@ int main(int argc, char **argv)
     }
     const std::string dir = argv[1], fasta = argv[2], mode = argv[3];
     if (mode != "query" && mode != "query_details" && mode != "query_best" && mode != "add" &&
-        mode != "matrix" && mode != "fq" && mode != "lookup") {
+        mode != "matrix" && mode != "fq" && mode != "lookup" && mode != "proteins") {
         std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
         return 2;
     }
@@ -87,6 +90,24 @@ int main(int argc, char **argv)
         std::stringstream ss;
         ss << in.rdbuf();
         const std::string body = ss.str();
+        if (mode == "proteins") {
+            kgx_f2p *h = nullptr;
+            const char *text = nullptr;
+            uint64_t n = 0;
+            int rc = kgx_f2p_create(kguts.ctx(), 0, &h);
+            if (!rc)
+                rc = kgx_f2p_process(h, body.data(), body.size(), 1, &text, &n);
+            if (rc) {
+                std::fprintf(stderr, "kgx_query: %s\n", kgx_last_error());
+                kgx_f2p_destroy(h);
+                return 1;
+            }
+            std::fwrite(text, 1, n, stdout);
+            if (*kgx_f2p_error(h))
+                std::fprintf(stderr, "%s\n", kgx_f2p_error(h));
+            kgx_f2p_destroy(h);
+            return 0;
+        }
         const work_list_t work = parse_fasta_body(body.data(), body.size());
         std::ostringstream os;
         if (mode == "lookup") {

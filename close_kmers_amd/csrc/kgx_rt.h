@@ -319,6 +319,9 @@ int fq_fragments_finish(kgx_ctx *c, kgx_fragments *out);
  * readable from d_bases (the DNA probe's limit) */
 int fq_fragments(kgx_ctx *c, const uint8_t *d_bases, const uint64_t *d_read_off, uint32_t n_reads,
                  uint64_t n_bases, uint64_t bound, kgx_fragments *out);
+/* kgx_fq_proteins behind its argument checks (kgx_fq.hip); the context's device is current */
+int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
+                const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out);
 /* kgx_stage_probe over fragments left as DNA (launch_probe_dna) */
 int stage_probe_dna(kgx_ctx *c, const uint8_t *bases, uint64_t n_bases, const uint64_t *anchors,
                     const uint64_t *d_off);
@@ -469,6 +472,14 @@ struct kgx_ctx {
     kgx::DevBuf fq_look; /* fq_fused: tile counter | tile states */
     kgx::PinnedVec<uint64_t> h_fq_tot; /* fragments, residues of the last fq batch */
     kgx::FqPending fq_pend;             /* an enqueued fragment pass awaiting its finish */
+    /* kgx_fq_proteins (kgx_fq.hip): the ids, per read its fragments and their
+     * scan, per (read, frame) its tokens, per fragment anchor / length / token
+     * / read / frame / record size, the record offsets and the text */
+    kgx::DevBuf ft_ids, ft_idoff, ft_rcnt, ft_rbase, ft_tok6, ft_anchor, ft_len, ft_token, ft_read, ft_frame,
+        ft_size, ft_off, ft_text;
+    kgx::PinnedVec<uint64_t> h_ft_idoff;
+    std::vector<hipEvent_t> ft_events; /* timing: start, uploaded, indexed, sized, written */
+    float ft_ms[4] = {0, 0, 0, 0};     /* upload, scan and indices, sizes, write of the last call */
     /* kgx_gunzip / kgx_gunzip_device (kgx_gunzip.cpp) */
     kgx::DevBuf gz_in, gz_out, gz_members, gz_status, gz_stats;
     kgx::PinnedVec<kgx_gz_member> h_gz_members;

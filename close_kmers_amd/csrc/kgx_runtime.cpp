@@ -1012,6 +1012,8 @@ int kgx_ctx_destroy(kgx_ctx *c)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : c->gz_events)
         (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ft_events)
+        (void)hipEventDestroy(e);
     if (c->copy_stream) {
         (void)hipStreamSynchronize(c->copy_stream);
         (void)hipStreamDestroy(c->copy_stream);

@@ -1046,6 +1046,65 @@ int kgx_fq_destroy(kgx_fq *fq);
 int kgx_fq_process(kgx_fq *fq, const char *fastq, uint64_t n, int finished, const char **text,
                    uint64_t *text_len);
 
+/* ---- reads -> six-frame protein FASTA (fastq_to_protein.cc)
+ * For every read with a non-empty id, in input order, and each frame 1, 2, 3,
+ * -1, -2, -3: the code-11 translation split at '*' as boost::split with
+ * token_compress_on does (a run of '*' is one separator; a separator at either
+ * end leaves an empty token there; an empty translation is one empty token),
+ * the frame's tokens numbered 1, 2, ... and every token longer than 10 residues
+ * written as
+ *     >ID:FRAME:INDEX\nTOKEN\n
+ * (fastq_to_protein.cc:24-47).  The fragments are kgx_fq_fragments' and come
+ * in its (read, frame, position) order.  Reads and ids are host arrays (bases
+ * and id bytes concatenated, read_offsets / id_offsets [n_reads + 1]); every
+ * output is on the device, owned by ctx and valid until its next fq call. */
+typedef struct kgx_fq_text {
+    uint32_t n_reads;
+    uint32_t n_fragments;
+    uint64_t n_bytes;        /* length of text = offsets[n_fragments] */
+    const char *text;        /* device: the records, back to back */
+    const uint64_t *offsets; /* device: [n_fragments + 1] record starts in text */
+    const uint32_t *read;    /* device: read index of each fragment */
+    const int8_t *frame;     /* device: its frame */
+    const uint32_t *token;   /* device: its INDEX, the token's number within the frame */
+} kgx_fq_text;
+int kgx_fq_proteins(kgx_ctx *ctx, const char *bases, const uint64_t *read_offsets, const char *ids,
+                    const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out);
+
+/* The tool as a streaming handle: FASTQ text in, FASTA text out.  Blocks may
+ * cut a record anywhere; `finished` ends the file and resets the parser and
+ * the error state for the next one.  Records are framed as the fq handler
+ * frames them, with the tool's two differences (fastq_parser.cc:17-36,
+ * fastq_to_protein.cc:49-53): the first parse error ends the parse -- the
+ * record in progress is translated with the id and bases it has and later
+ * blocks of the file yield nothing -- and at the end of the input the record
+ * in progress is translated if it has an id.  A file that starts 1f 8b 08 is
+ * gzip, sniffed as kgx_fq_process sniffs it: each block's complete members are
+ * inflated (kgx_gunzip on ctx) and their text processed.  part_bytes bounds
+ * the FASTQ text taken per device pass (0: 32 MB, as the fq handler).  *text
+ * is pinned host memory owned by the handle, valid until its next call.  One
+ * context, no overlap of one part's download with the next part's kernels. */
+typedef struct kgx_f2p kgx_f2p;
+typedef struct kgx_f2p_stats { /* since create or the last file's `finished` call, that call included */
+    uint64_t reads;            /* records parsed */
+    uint64_t reads_no_id;      /* of them skipped for an empty id */
+    uint64_t fragments;
+    uint64_t text_bytes;
+    uint64_t parts;            /* device passes */
+    uint32_t error_line;       /* line of the parse error (0: none) */
+    uint32_t gzip;             /* 1: the file was gzip */
+    /* parse on the host (wall clock); the others stream time (HIP events) */
+    double parse_ms, upload_ms, index_ms, sizes_ms, write_ms, download_ms;
+} kgx_f2p_stats;
+int kgx_f2p_create(kgx_ctx *ctx, uint64_t part_bytes, kgx_f2p **out);
+int kgx_f2p_destroy(kgx_f2p *h);
+int kgx_f2p_process(kgx_f2p *h, const char *fastq, uint64_t n, int finished, const char **text, uint64_t *text_len);
+/* the file being read, or after `finished` the file just ended */
+int kgx_f2p_get_stats(const kgx_f2p *h, kgx_f2p_stats *out);
+/* the reference's report of that file's parse error, "Error found: ... at line
+ * N id='...'" ("" if none); owned by the handle */
+const char *kgx_f2p_error(const kgx_f2p *h);
+
 /* ---- gzip (RFC 1952) and DEFLATE (RFC 1951) -------------------------------
  * The fq handler takes gzip bodies as the reference does
  * (fq_process_request.cc:64-104: a request whose first bytes are 1f 8b is

@@ -2,7 +2,7 @@
 # One GPU-box pass (run through gpurun from the repo root):
 #   bash tools/gpu_check.sh TAG [quick]
 # 1. the -m gpu test suite + smoke   2. bench.py (C2, with its canary)   3. C3 /matrix
-# 4. C4 fq (device pass and the handler over all reads)   5. HTTP serving (/query; /lookup in family mode)
+# 4. C4 fq (device pass and the handler over all reads; fastq_to_protein over the same reads)   5. HTTP serving (/query; /lookup in family mode)
 # 6. per-sequence facade calls (and with OTU stats, and batches beside the service)
 # 7. kgx_pool (C5 batch): contexts of one device, and bench.py --pool-devices 2
 # 8. call-service OTU phases; the host path by staging threads and H2D order
@@ -24,6 +24,7 @@ timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/sm
 timeout -k 10 900 python3 bench.py --full $NOCPU > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout -k 10 600 python3 tools/bench_matrix.py $NOCPU > "$OUT/bench_matrix.json" 2> "$OUT/bench_matrix.err"
 timeout -k 10 900 python3 tools/bench_fq.py $NOCPU > "$OUT/bench_fq.json" 2> "$OUT/bench_fq.err"
+timeout -k 10 600 python3 tools/bench_fastq_to_protein.py > "$OUT/bench_fastq_to_protein.json" 2> "$OUT/bench_fastq_to_protein.err"
 timeout -k 10 600 python3 tools/bench_server.py > "$OUT/bench_server.json" 2> "$OUT/bench_server.err"
 timeout -k 10 900 python3 tools/bench_server.py --families 100000 --path "/lookup?family_mode=1&find_best_match=1" \
     --clients 1,8,16 --threads 16 > "$OUT/bench_lookup_fam.json" 2> "$OUT/bench_lookup_fam.err"
