@@ -413,9 +413,15 @@ __global__ __launch_bounds__(256) void rollup_events_kernel(Tiled t, uint64_t n_
  * and entries are added in first-touch order.  Rows go to rows2[sfirst + q]
  * for the q-th entry.  A sequence with more distinct ids than one table pass
  * holds is taken in P id classes, each class's rows placed at their first
- * event's position (flag, rowdata) and compacted in event order after. */
+ * event's position (flag, rowdata) and compacted in event order after.  P
+ * doubles while a class overflows, up to kRollMaxP; ids that no doubling
+ * separates are then taken kRollFill at a time in first-touch order, each
+ * pass marking its ids' events done. */
 constexpr uint32_t kRollH = 256;    /* LDS table slots per wave */
 constexpr uint32_t kRollFill = 192; /* ids per table pass */
+constexpr uint32_t kRollMaxP = 16;  /* most id classes; past it, passes by first touch */
+constexpr uint8_t kRollRow = 1;     /* flag: a row's first event */
+constexpr uint8_t kRollDone = 2;    /* flag: the event's id is summed (passes by first touch) */
 
 __device__ __forceinline__ uint32_t roll_hash(uint32_t id) { return (id * 0x9E3779B1u) >> 24; }
 __device__ __forceinline__ uint32_t roll_class(uint32_t id, uint32_t P) { return ((id * 0x85EBCA6Bu) >> 13) & (P - 1); }
@@ -443,54 +449,81 @@ __global__ __launch_bounds__(256) void rollup_group_kernel(uint32_t n_seq, const
     auto row = [&](uint32_t h) {
         return family ? make_uint4(K[h], C[h], C[h], __float_as_uint(Wt[h])) : make_uint4(K[h], C[h], 0u, 0u);
     };
+    /* One table pass over the sequence's events.  By class (rest = false):
+     * the ids of class p of P; false as soon as one more id than the table
+     * holds turns up.  By rest (rest = true): the events not yet marked done,
+     * whose first kRollFill distinct ids in first-touch order enter the table
+     * and are summed over the whole range; later ids are left for another
+     * pass, and false says there are some. */
+    uint32_t used = 0;
+    auto table_pass = [&](uint32_t p, uint32_t P, auto rest_c) -> bool {
+        constexpr bool rest = decltype(rest_c)::value;
+        for (uint32_t i = lane; i < kRollH; i += 64)
+            K[i] = NO_ID;
+        __builtin_amdgcn_wave_barrier();
+        used = 0;
+        bool fit = true;
+        for (uint32_t e = f; e < l && (rest || fit); e += 64) {
+            const uint32_t i = e + lane;
+            const bool valid = i < l;
+            const uint32_t id = valid ? ev_id[i] : NO_ID;
+            const float w = valid ? ev_w[i] : 0.0f;
+            bool mine;
+            if constexpr (rest)
+                mine = valid && !(flag[i] & kRollDone);
+            else
+                mine = valid && roll_class(id, P) == p;
+            uint64_t rem = __ballot(mine);
+            while (rem) {
+                const uint32_t ld = (uint32_t)__builtin_ctzll(rem);
+                const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)ld);
+                const uint64_t grp = __ballot(mine && id == lid);
+                rem &= ~grp;
+                uint32_t h = roll_hash(lid);
+                uint32_t kh;
+                while ((kh = K[h]) != NO_ID && kh != lid)
+                    h = (h + 1) & (kRollH - 1);
+                const bool fresh = kh == NO_ID;
+                if (fresh && used == kRollFill) {
+                    fit = false; /* too many ids for one pass */
+                    if constexpr (rest)
+                        continue;
+                    else
+                        break;
+                }
+                float sum = fresh ? 0.0f : Wt[h];
+                const uint32_t cnt = (fresh ? 0u : C[h]) + (uint32_t)__popcll(grp);
+                for (uint64_t g = grp; g; g &= g - 1) {
+                    const int b = (int)__builtin_ctzll(g);
+                    sum += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), b)); /* hit by hit */
+                }
+                if (lane == 0) {
+                    if (fresh) {
+                        K[h] = lid;
+                        F[h] = e + ld - f;
+                        L[used] = h;
+                    }
+                    C[h] = cnt;
+                    Wt[h] = sum;
+                }
+                used += fresh;
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        return fit;
+    };
+    /* Bound on passes, whatever the ids: P doubles from 1 to kRollMaxP, at
+     * most 2 * kRollMaxP - 1 = 31 class passes in all (P never wraps); when a
+     * class of kRollMaxP still overflows (ids that share their class bits
+     * cannot be split by doubling), the sequence is finished by rest passes,
+     * which need no hash to make progress: each takes kRollFill new ids while
+     * there are that many, so there are ceil(distinct ids / kRollFill). */
     uint32_t P = 1, nrows = 0;
+    bool by_rest = false;
     for (;;) {
         bool ok = true;
         for (uint32_t p = 0; p < P && ok; p++) {
-            for (uint32_t i = lane; i < kRollH; i += 64)
-                K[i] = NO_ID;
-            __builtin_amdgcn_wave_barrier();
-            uint32_t used = 0;
-            for (uint32_t e = f; e < l && ok; e += 64) {
-                const uint32_t i = e + lane;
-                const bool valid = i < l;
-                const uint32_t id = valid ? ev_id[i] : NO_ID;
-                const float w = valid ? ev_w[i] : 0.0f;
-                const bool mine = valid && roll_class(id, P) == p;
-                uint64_t rem = __ballot(mine);
-                while (rem) {
-                    const uint32_t ld = (uint32_t)__builtin_ctzll(rem);
-                    const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)ld);
-                    const uint64_t grp = __ballot(mine && id == lid);
-                    rem &= ~grp;
-                    uint32_t h = roll_hash(lid);
-                    uint32_t kh;
-                    while ((kh = K[h]) != NO_ID && kh != lid)
-                        h = (h + 1) & (kRollH - 1);
-                    const bool fresh = kh == NO_ID;
-                    if (fresh && used == kRollFill) {
-                        ok = false; /* too many ids for one pass: classes */
-                        break;
-                    }
-                    float sum = fresh ? 0.0f : Wt[h];
-                    const uint32_t cnt = (fresh ? 0u : C[h]) + (uint32_t)__popcll(grp);
-                    for (uint64_t g = grp; g; g &= g - 1) {
-                        const int b = (int)__builtin_ctzll(g);
-                        sum += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), b)); /* hit by hit */
-                    }
-                    if (lane == 0) {
-                        if (fresh) {
-                            K[h] = lid;
-                            F[h] = e + ld - f;
-                            L[used] = h;
-                        }
-                        C[h] = cnt;
-                        Wt[h] = sum;
-                    }
-                    used += fresh;
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
+            ok = table_pass(p, P, std::false_type{});
             if (!ok)
                 break;
             if (P == 1) {
@@ -508,9 +541,37 @@ __global__ __launch_bounds__(256) void rollup_group_kernel(uint32_t n_seq, const
         }
         if (ok)
             break;
-        P *= 2;
         for (uint32_t i = f + lane; i < l; i += 64)
             flag[i] = 0;
+        if (P == kRollMaxP) {
+            by_rest = true;
+            break;
+        }
+        P *= 2;
+    }
+    if (by_rest) {
+        /* flag[i] and rowdata[i] are only ever touched by lane (i - f) % 64
+         * from here on, so a lane sees its own marks in program order */
+        bool more;
+        do {
+            more = !table_pass(0, 0, std::true_type{});
+            for (uint32_t e = f; e < l; e += 64) {
+                const uint32_t i = e + lane;
+                if (i < l && !(flag[i] & kRollDone)) {
+                    const uint32_t id = ev_id[i];
+                    uint32_t h = roll_hash(id), kh; /* at most kRollFill of kRollH slots are taken */
+                    while ((kh = K[h]) != NO_ID && kh != id)
+                        h = (h + 1) & (kRollH - 1);
+                    if (kh == id) { /* summed by this pass; its first event carries the row */
+                        const bool first = F[h] == i - f;
+                        if (first)
+                            rowdata[i] = row(h);
+                        flag[i] = first ? (kRollDone | kRollRow) : kRollDone;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        } while (more);
     }
     if (P > 1) {
         /* the classes' rows in first-event order (this wave's own stores) */
@@ -519,7 +580,7 @@ __global__ __launch_bounds__(256) void rollup_group_kernel(uint32_t n_seq, const
         uint32_t rank = 0;
         for (uint32_t e = f; e < l; e += 64) {
             const uint32_t i = e + lane;
-            const bool fl = i < l && flag[i];
+            const bool fl = i < l && (flag[i] & kRollRow);
             const uint64_t bm = __ballot(fl);
             if (fl)
                 rows2[f + rank + lanes_below(bm)] = rowdata[i];

@@ -131,6 +131,8 @@ def lib():
         L.oracle_kmap_lookup.restype = u64
         L.oracle_kmap_num_kmers.argtypes = [vp]
         L.oracle_kmap_num_kmers.restype = u64
+        L.oracle_lookup_rollup.argtypes = [vp, ctypes.c_int, u64, vp, vp, vp]
+        L.oracle_lookup_rollup.restype = vp
         L.oracle_matrix_new.restype = vp
         L.oracle_matrix_free.argtypes = [vp]
         L.oracle_matrix_add.argtypes = [vp, vp, vp, vp, u64, vp, vp]
@@ -377,6 +379,30 @@ class Kmap:
         if getattr(self, "h", None):
             lib().oracle_kmap_free(self.h)
             self.h = None
+
+
+ROLLUP_DTYPE = np.dtype([("id", "<u4"), ("hit_count", "<u4"), ("hit_total", "<u4"), ("weighted_total", "<f4")])
+
+
+def lookup_rollup(kmap: Kmap, hit_offsets, hit_kmers, family: bool):
+    """LookupRequest::on_hit (lookup_request.cc:446-482) over a batch's hits
+    (sequence s: hit_kmers[hit_offsets[s]:hit_offsets[s + 1]] in position
+    order): (row_offsets[n_seq + 1], rows) with one ROLLUP_DTYPE row per id a
+    sequence touched, in first-touch order; weighted_total summed in f32 hit
+    by hit.  The same function as the /lookup text handler's."""
+    off = np.ascontiguousarray(hit_offsets, dtype=np.uint64)
+    km = np.ascontiguousarray(hit_kmers, dtype=np.uint64)
+    n = len(off) - 1
+    assert n >= 0 and int(off[-1]) <= len(km)
+    row_off = np.zeros(n + 1, np.uint64)
+    p = lib().oracle_lookup_rollup(kmap.h, 1 if family else 0, n, off.ctypes.data,
+                                   km.ctypes.data if len(km) else None, row_off.ctypes.data)
+    if not p:
+        raise MemoryError("oracle_lookup_rollup")
+    try:
+        return row_off, _arr(p, int(row_off[-1]), ROLLUP_DTYPE)
+    finally:
+        lib().oracle_free(p)
 
 
 class Matrix:

@@ -444,6 +444,30 @@ struct LookupSession {
     ~LookupSession() { delete scorer; }
 };
 
+/* LookupRequest::on_hit (lookup_request.cc:446-482) for one hit's k-mer:
+ * score_of(id) is the sequence's accumulator of `id` (seq_score_[id], made on
+ * first touch).  The text handler below and oracle_lookup_rollup both come
+ * through here, so the golden /lookup texts pin what the batch entry adds. */
+template <class ScoreOf>
+static void lookup_on_hit(const Kmap &map, uint64_t kmer, bool family_mode, ScoreOf &&score_of)
+{
+    auto ki = map.m.find(kmer);
+    if (ki == map.m.end())
+        return;
+    if (family_mode) {
+        const float weight = 1.0f / (float)ki->second.size();
+        for (uint32_t ent : ki->second) {
+            AccScore &s = score_of(ent);
+            s.hit_count++;
+            s.hit_total++;
+            s.weighted_total += weight;
+        }
+    } else {
+        for (uint32_t eid : ki->second)
+            score_of(eid).hit_count++;
+    }
+}
+
 /* one /lookup request over FASTA records (lookup_request.cc) */
 static std::string lookup_request(LookupSession &q, bool family_mode,
                                   const std::map<std::string, std::string> &params,
@@ -479,26 +503,9 @@ static std::string lookup_request(LookupSession &q, bool family_mode,
         std::vector<oracle::SeqHit> hits;
         const bool want_calls = find_best_match && family_mode;
         q.scorer->process(seq.c_str(), seq.size(), want_calls ? &calls : nullptr, &hits, nullptr, true);
-        for (auto &h : hits) { /* on_hit, lookup_request.cc:446-482 */
-            if (family_mode) {
-                auto ki = q.db.kmer_to_family.m.find(h.hit.which_kmer);
-                if (ki == q.db.kmer_to_family.m.end())
-                    continue;
-                const float weight = 1.0f / (float)ki->second.size();
-                for (uint32_t ent : ki->second) {
-                    AccScore &s = seq_score[ent];
-                    s.hit_count++;
-                    s.hit_total++;
-                    s.weighted_total += weight;
-                }
-            } else {
-                auto ki = q.kmer_to_id.m.find(h.hit.which_kmer);
-                if (ki == q.kmer_to_id.m.end())
-                    continue;
-                for (uint32_t eid : ki->second)
-                    seq_score[eid].hit_count++;
-            }
-        }
+        const Kmap &map = family_mode ? q.db.kmer_to_family : q.kmer_to_id;
+        for (auto &h : hits)
+            lookup_on_hit(map, h.hit.which_kmer, family_mode, [&](uint32_t id) -> AccScore & { return seq_score[id]; });
         if (find_best_match && family_mode) {
             int fi;
             std::string fn;
@@ -641,6 +648,47 @@ uint64_t oracle_kmap_lookup(void *p, uint64_t kmer, uint32_t *ids, uint64_t cap)
 }
 
 uint64_t oracle_kmap_num_kmers(void *p) { return static_cast<Kmap *>(p)->m.size(); }
+
+/* on_hit over a batch: sequence s has the hits hit_kmers[hit_off[s] ..
+ * hit_off[s+1]) in position order.  Its accumulators, one row each of (id,
+ * hit_count, hit_total, weighted_total as f32) in first-touch order, go to
+ * rows [row_off[s], row_off[s+1]); returns the rows (oracle_free). */
+void *oracle_lookup_rollup(void *pk, int family_mode, uint64_t n_seq, const uint64_t *hit_off,
+                           const uint64_t *hit_kmers, uint64_t *row_off)
+{
+    struct Row {
+        uint32_t id, hit_count, hit_total;
+        float weighted_total;
+    };
+    static_assert(sizeof(Row) == 16, "kgx_rollup_row layout");
+    const Kmap &map = *static_cast<Kmap *>(pk);
+    std::vector<Row> rows;
+    std::vector<AccScore> acc;                  /* this sequence's, in first-touch order */
+    std::vector<uint32_t> ids;
+    std::unordered_map<uint32_t, size_t> where; /* id -> index in acc */
+    row_off[0] = 0;
+    for (uint64_t s = 0; s < n_seq; s++) {
+        acc.clear();
+        ids.clear();
+        where.clear();
+        for (uint64_t h = hit_off[s]; h < hit_off[s + 1]; h++)
+            lookup_on_hit(map, hit_kmers[h], family_mode != 0, [&](uint32_t id) -> AccScore & {
+                auto ins = where.emplace(id, acc.size());
+                if (ins.second) {
+                    acc.emplace_back();
+                    ids.push_back(id);
+                }
+                return acc[ins.first->second];
+            });
+        for (size_t i = 0; i < acc.size(); i++)
+            rows.push_back(Row{ids[i], acc[i].hit_count, acc[i].hit_total, acc[i].weighted_total});
+        row_off[s + 1] = rows.size();
+    }
+    void *out = std::malloc(std::max<size_t>(1, rows.size() * sizeof(Row)));
+    if (out && !rows.empty())
+        std::memcpy(out, rows.data(), rows.size() * sizeof(Row));
+    return out;
+}
 
 void *oracle_matrix_new(void) { return new Matrix; }
 void oracle_matrix_free(void *p) { delete static_cast<Matrix *>(p); }

@@ -4,12 +4,14 @@ lookup_request.cc:153-210,446-482) and caller-pinned residues (context
 option "pinned_input": no staging copy, a device NUL scan, a staged rerun on
 a NUL -- the strlen bound of kguts.cc:792).
 
-Rows are checked against one context's pass + kgx_kmap_rollup, and a slice
-against on_hit replayed over the oracle's hits (the same restatement
+Rows are checked against one context's pass + kgx_kmap_rollup, against the
+oracle's on_hit for every sequence (rollup_yardstick.py), and a slice against
+on_hit replayed in Python over the oracle's hits (the restatement
 test_gpu_tables.py uses)."""
 import numpy as np
 import pytest
 
+import rollup_yardstick
 from close_kmers_amd import abi, synth
 from helpers import synthetic_table
 from test_gpu_tables import _on_hit_rollup
@@ -81,6 +83,9 @@ def test_pool_lookup_matches_one_context_and_on_hit(world, oracle_lib, n_ctx, pi
             assert g["hit_total"].tolist() == [v[1] for v in exp.values()], s
             w = np.array([v[2] for v in exp.values()], np.float32)
             assert np.array_equal(g["weighted_total"].view(np.uint32), w.view(np.uint32)), s
+        # every sequence against the oracle's on_hit
+        rollup_yardstick.assert_rows(roff, rows, *rollup_yardstick.expected(oracle_lib, table, res, off, keys, ids,
+                                                                            True), what="pool, all sequences")
 
 
 def _compact_bytes(cb, res, off):

@@ -151,13 +151,9 @@ def _on_hit_rollup(hit_kmers, orc_kmap, family):
     return d
 
 
-@pytest.mark.parametrize("mode", [0, 1])
-def test_kmap_rollup_matches_on_hit(table_world, gpu, oracle_lib, mode):
-    """Device rollups (kgx_kmap_rollup) == on_hit replayed over the oracle's
-    hits and lists: k-mers mapping to 1-9 ids out of a small pool (tied
-    weighted totals), repeated ids in peg lists, unmapped hits, empty and
-    hit-free sequences, ids with a high bit."""
-    spec, table, img, ctx = table_world
+def on_hit_corpus(spec, table, oracle_lib, mode):
+    """The corpus of test_kmap_rollup_matches_on_hit: sequences, the oracle's
+    hits (offsets, k-mers), the packed batch and the (k-mer, id) pairs."""
     rng = np.random.default_rng(31 + mode)
     seqs = _family_proteins(spec, rng, 14, 4) + [b"", b"ACDEFGH", bytes(synth.ALPHA[rng.integers(0, 20, 400)])]
     order = rng.permutation(len(seqs))
@@ -172,7 +168,17 @@ def test_kmap_rollup_matches_on_hit(table_world, gpu, oracle_lib, mode):
         sel = pool[rng.integers(0, len(pool), n)]
         kms.append(np.full(n, k, np.uint64))
         ids.append(sel)
-    kms, ids = np.concatenate(kms), np.concatenate(ids)
+    return seqs, hoff, hk, res, off, np.concatenate(kms), np.concatenate(ids)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_kmap_rollup_matches_on_hit(table_world, gpu, oracle_lib, mode):
+    """Device rollups (kgx_kmap_rollup) == on_hit replayed over the oracle's
+    hits and lists: k-mers mapping to 1-9 ids out of a small pool (tied
+    weighted totals), repeated ids in peg lists, unmapped hits, empty and
+    hit-free sequences, ids with a high bit."""
+    spec, table, img, ctx = table_world
+    seqs, hoff, hk, res, off, kms, ids = on_hit_corpus(spec, table, oracle_lib, mode)
     orc = oracle_lib.Kmap(1 if mode == 1 else 0)
     orc.add(kms, ids)
     family = mode == gpu.ROLLUP_FAMILY
@@ -200,12 +206,8 @@ def test_kmap_rollup_matches_on_hit(table_world, gpu, oracle_lib, mode):
         assert len(rows) == 0 and not roff.any()
 
 
-def test_kmap_rollup_many_ids_and_resizing(table_world, gpu, oracle_lib):
-    """Sequences with hundreds to thousands of distinct ids (more than one LDS
-    table pass holds: the id-class path) and a context whose batches grow and
-    shrink between rollups (a rollup sized by the previous event count, then
-    one too small for its batch, which runs again at the true size)."""
-    spec, table, img, ctx = table_world
+def many_ids_corpus(spec, table, oracle_lib):
+    """The corpus of test_kmap_rollup_many_ids_and_resizing, as on_hit_corpus."""
     rng = np.random.default_rng(77)
     fam = _family_proteins(spec, rng, 8, 2)
     long_seqs = [b"".join(fam[i:i + 4]) for i in range(0, 8, 4)]  # ~1,100-1,200 aa
@@ -217,7 +219,16 @@ def test_kmap_rollup_many_ids_and_resizing(table_world, gpu, oracle_lib):
         n = int(rng.integers(1, 10))
         kms.append(np.full(n, k, np.uint64))
         ids.append(rng.integers(0, 50000, n).astype(np.uint32))
-    kms, ids = np.concatenate(kms), np.concatenate(ids)
+    return seqs, hoff, hk, res, off, np.concatenate(kms), np.concatenate(ids)
+
+
+def test_kmap_rollup_many_ids_and_resizing(table_world, gpu, oracle_lib):
+    """Sequences with hundreds to thousands of distinct ids (more than one LDS
+    table pass holds: the id-class path) and a context whose batches grow and
+    shrink between rollups (a rollup sized by the previous event count, then
+    one too small for its batch, which runs again at the true size)."""
+    spec, table, img, ctx = table_world
+    seqs, hoff, hk, res, off, kms, ids = many_ids_corpus(spec, table, oracle_lib)
     orc = oracle_lib.Kmap(1)
     orc.add(kms, ids)
 
