@@ -557,6 +557,7 @@ private:
  * (one FamilyMapper per block, as process_data constructs one,
  * fq_process_request.cc:241).
  */
+class GzipBodyReader;
 class FqRequest {
 public:
     FqRequest(KmerGuts &kg, std::shared_ptr<KmerPegMapping> mapping);
@@ -589,28 +590,12 @@ private:
         const char *id(size_t r) const { return ids + id_off[r]; }
         size_t id_len(size_t r) const { return (size_t)(id_off[r + 1] - id_off[r]); }
     };
-    /* one part of a block, parsed: its reads' bases in pinned host memory
-     * (kgx_host_alloc; the device copies them from there), offsets, ids, and
-     * the parser state at its end.  Kept across blocks (buffers reused). */
-    struct FqPart {
-        int state = 0;
-        std::string id;
-        char *bases = nullptr;
-        size_t cap = 0, len = 0;
-        std::vector<uint64_t> roff{0}, id_off{0};
-        std::string id_chars;
-        FqPart() = default;
-        FqPart(const FqPart &) = delete;
-        FqPart &operator=(const FqPart &) = delete;
-        ~FqPart();
-        /* empty, from a parser state, room for `need` bases */
-        void begin(size_t need, int state, const std::string &carried_id, const std::string &carried_bases);
-        void parse(const char *a, const char *b);
-        FqBlock view() const;
-    };
+    /* one part of a block, parsed, and the source of a block's parts: the
+     * cuts, the parallel parse ahead and its pinned buffers (kguts_fq.cpp) */
+    struct FqPart;
+    class FqParts;
     /* one block of text (process() after the sniff and the inflate) */
     void process_text(const char *text, size_t n, bool finished, std::ostream &os);
-    void process_gzip(const char *block, size_t n, bool finished, std::ostream &os);
     void process_block(const FqBlock &blk, FamilyMapper &mapper, std::ostream &os);
     /* process_block in two halves: launch sizes the block's fragments and
      * enqueues their lookup on ctx; finish collects the results and writes the
@@ -621,33 +606,26 @@ private:
         uint32_t n_reads = 0;
         kgx_fragments fr{};
     };
-    FqLaunched launch_block(const FqBlock &blk, kgx_ctx *ctx);
-    /* after kgx_fq_upload on ctx: enqueue the fragment pass over those reads */
-    void start_fragments(kgx_ctx *ctx);
-    /* launch_block's second half, after kgx_fq_upload and start_fragments of
-     * l's reads on l.ctx: the pass's sizes, then the lookup enqueued */
+    /* the block's reads up to ctx by DMA and the fragment pass over them
+     * enqueued behind the upload: a part's pass runs while the GPU still
+     * probes the part before it */
+    FqLaunched upload_block(const FqBlock &blk, kgx_ctx *ctx);
+    /* after upload_block: the pass's sizes, then the lookup enqueued */
     void launch_uploaded(FqLaunched &l);
+    /* upload_block, then launch_uploaded */
+    FqLaunched launch_block(const FqBlock &blk, kgx_ctx *ctx);
     void finish_block(const FqBlock &blk, FqLaunched &l, FamilyMapper &mapper, std::ostream &os);
-    kgx_ctx *twin_ctx(); /* a second context on the image, created on first use */
-    kgx_ctx *twin_ = nullptr;
-    kgx_ctx *twin2_ctx(); /* a third, for the multi-part pipeline */
-    kgx_ctx *twin2_ = nullptr;
+    /* context i of the multi-part rotation: 0 is kg_'s, 1 and 2 further ones
+     * on the image, created on first use */
+    kgx_ctx *rotation_ctx(size_t i);
+    kgx_ctx *twin_[2] = {nullptr, nullptr};
     KmerGuts &kg_;
     std::shared_ptr<KmerPegMapping> mapping_;
     /* FastqParser state (fastq_parser.h:40-150) */
     int state_ = 0;
     std::string id_, seq_;
-    std::vector<std::unique_ptr<FqPart>> parts_;
-    /* the exact re-parse after a rejected speculative cut: kept, so its pinned
-     * buffer is allocated once, not per fallback */
-    std::unique_ptr<FqPart> tail_;
-    /* gzip requests */
-    enum { BODY_UNKNOWN, BODY_HELD, BODY_TEXT, BODY_GZIP };
-    int body_ = BODY_UNKNOWN;  /* of the request in progress; BODY_HELD: fewer than 10 bytes so far, the first 1f */
-    std::string gz_tail_;      /* compressed bytes not consumed yet */
-    uint64_t gz_members_ = 0;  /* members inflated so far in this request */
-    char *gz_text_ = nullptr;  /* inflated text, pinned (kgx_host_alloc) */
-    size_t gz_text_cap_ = 0;
+    std::unique_ptr<FqParts> parts_; /* kept across blocks: its pinned buffers are reused */
+    std::unique_ptr<GzipBodyReader> body_; /* text or gzip: the sniff and the inflate (kgx_gzip.h) */
 };
 
 /* one host-buffer batch through kg's context, device results only (no D2H):

@@ -1,7 +1,8 @@
 /*
  * kgx_f2p.cpp -- fastq_to_protein as a streaming handle (include/kgx.h
- * kgx_f2p_*): FASTQ text in blocks -> the strict parser
- * (kgx_fq_parse.h) -> parts of at most part_bytes of text -> kgx_fq_proteins on
+ * kgx_f2p_*): FASTQ in blocks, text or gzip (the front end
+ * it shares with the fq handler of kguts_fq.cpp: GzipBodyReader, kgx_gzip.h)
+ * -> the strict parser (kgx_fq_parse.h) -> parts of at most part_bytes of text -> kgx_fq_proteins on
  * the handle's context -> the part's text copied into pinned host memory.
  * One context and one part at a time: a part's download does not overlap the
  * next part's kernels.
@@ -9,6 +10,7 @@
 #include <chrono>
 
 #include "kgx_fq_parse.h"
+#include "kgx_gzip.h"
 #include "kgx_rt.h"
 
 using namespace kgx;
@@ -16,11 +18,7 @@ using namespace kgx;
 struct kgx_f2p {
     kgx_ctx *ctx = nullptr;
     uint64_t part_bytes = 0;
-    /* the body of the file being read: decided by its first bytes */
-    enum { BODY_UNKNOWN, BODY_HELD, BODY_TEXT, BODY_GZIP } body = BODY_UNKNOWN;
-    std::string gz_tail;     /* held first bytes / compressed bytes of an incomplete member */
-    uint64_t gz_members = 0; /* members inflated so far */
-    PinnedVec<char> gz_text; /* a block's inflated text */
+    GzipBodyReader body; /* the file being read, text or gzip: decided by its first bytes */
     /* the part being parsed */
     FqStrict ps;
     PinnedVec<char> bases;
@@ -114,49 +112,10 @@ int process_text(kgx_f2p *h, const char *text, size_t n, bool finished)
     return KGX_OK;
 }
 
-/* the block's complete gzip members -> text -> process_text (FqRequest::process_gzip) */
-int process_gzip(kgx_f2p *h, const char *block, size_t n, bool finished)
-{
-    if (h->ps.stopped) /* after a parse error nothing more is read */
-        return KGX_OK;
-    h->gz_tail.append(block, n);
-    /* trailing bytes after a member that are no gzip are ignored, as gzip does */
-    if (h->gz_members && h->gz_tail.size() >= 2 &&
-        !((unsigned char)h->gz_tail[0] == 0x1f && (unsigned char)h->gz_tail[1] == 0x8b))
-        h->gz_tail.clear();
-    uint64_t members = 0, blocked = 0, out_bytes = 0, consumed = 0, out_len = 0;
-    if (int rc = kgx_gunzip_scan(h->gz_tail.data(), h->gz_tail.size(), finished, &members, &blocked, &out_bytes,
-                                 &consumed))
-        return rc;
-    /* blocked members state their sizes; a plain member's is found by trying */
-    size_t cap = (size_t)out_bytes + 64;
-    if (members > blocked && finished)
-        cap += 6 * h->gz_tail.size() + (size_t(1) << 20);
-    for (;;) {
-        h->gz_text.n = 0; /* nothing to keep when it grows */
-        HIP_TRY(h->gz_text.resize(cap));
-        kgx_gunzip_stats gs;
-        const int rc = kgx_gunzip(h->ctx, h->gz_tail.data(), h->gz_tail.size(), finished, h->gz_text.data(), cap,
-                                  &out_len, &consumed, &gs);
-        if (rc == KGX_ERANGE && members > blocked) {
-            cap *= 2;
-            continue;
-        }
-        if (rc)
-            return rc;
-        h->gz_members += gs.members;
-        break;
-    }
-    h->gz_tail.erase(0, (size_t)consumed);
-    return process_text(h, h->gz_text.data(), (size_t)out_len, finished);
-}
-
 /* the file ends, in its last block or in an error: the next call starts one */
 void end_file(kgx_f2p *h)
 {
-    h->body = kgx_f2p::BODY_UNKNOWN;
-    h->gz_tail.clear();
-    h->gz_members = 0;
+    h->body.reset();
     h->ps.reset();
     h->n_bases = 0;
     h->roff.assign(1, 0);
@@ -166,41 +125,21 @@ void end_file(kgx_f2p *h)
     h->ended = true;
 }
 
-/* the sniff at the start of a file, as FqRequest::process: 1f 8b 08 makes the
- * whole file gzip; a first block shorter than gzip's fixed header that begins
- * with 1f is held until more arrives or the file ends */
+/* a block of the file, text or gzip (GzipBodyReader sniffs the file's start
+ * and inflates a block's complete members), through process_text */
 int process_block(kgx_f2p *h, const char *block, size_t n, bool finished)
 {
-    if (h->body == kgx_f2p::BODY_UNKNOWN || h->body == kgx_f2p::BODY_HELD) {
-        const std::string &held = h->gz_tail;
-        auto byte = [&](size_t i) { return (unsigned char)(i < held.size() ? held[i] : block[i - held.size()]); };
-        const size_t have = held.size() + n;
-        if (have == 0 || byte(0) != 0x1f)
-            h->body = kgx_f2p::BODY_TEXT;
-        else if (have >= 3)
-            h->body = byte(1) == 0x8b && byte(2) == 8 ? kgx_f2p::BODY_GZIP : kgx_f2p::BODY_TEXT;
-        else if (finished)
-            h->body = kgx_f2p::BODY_TEXT;
-        else
-            h->body = kgx_f2p::BODY_HELD;
-        if (h->body == kgx_f2p::BODY_GZIP && have < 10 && !finished)
-            h->body = kgx_f2p::BODY_HELD;
-        if (h->body == kgx_f2p::BODY_HELD) {
-            h->gz_tail.append(block, n);
-            return KGX_OK;
-        }
-        if (h->body == kgx_f2p::BODY_TEXT && !h->gz_tail.empty()) { /* held bytes that were text after all */
-            std::string all;
-            all.swap(h->gz_tail);
-            all.append(block, n);
-            return process_text(h, all.data(), all.size(), finished);
-        }
-    }
-    if (h->body == kgx_f2p::BODY_GZIP) {
+    if (h->ps.stopped && h->body.body() == GZ_BODY_GZIP) /* after a parse error nothing more is inflated */
+        return KGX_OK;
+    const char *text = nullptr;
+    size_t len = 0;
+    if (int rc = h->body.feed(h->ctx, block, n, finished, true, &text, &len))
+        return rc;
+    if (!text) /* held: too short to tell yet */
+        return KGX_OK;
+    if (h->body.gzip())
         h->st.gzip = 1;
-        return process_gzip(h, block, n, finished);
-    }
-    return process_text(h, block, n, finished);
+    return process_text(h, text, len, finished);
 }
 
 }  // namespace

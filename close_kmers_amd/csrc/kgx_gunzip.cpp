@@ -3,7 +3,8 @@
  * the framing walk over a body's members (kgx_gzip.h), blocked members
  * through the device kernel (kgx_inflate.hip) or over host threads, plain
  * members on the calling thread.  One decoder source for all of them
- * (kgx_inflate.h); no zlib.
+ * (kgx_inflate.h); no zlib.  Over them, GzipBodyReader: the text-or-gzip
+ * front end of the fq handler and of fastq_to_protein.
  */
 #include <hip/hip_runtime.h>
 
@@ -367,3 +368,97 @@ int kgx_gunzip(kgx_ctx *c, const void *gz, uint64_t n, int finished, void *out, 
 }
 
 }  // extern "C"
+
+/* ---- GzipBodyReader (kgx_gzip.h), over the entry points above ------------- */
+
+namespace kgx {
+
+GzipBodyReader::~GzipBodyReader()
+{
+    if (text_)
+        kgx_host_free(text_);
+}
+
+void GzipBodyReader::reset()
+{
+    body_ = GZ_BODY_UNKNOWN;
+    tail_.clear();
+    members_ = 0;
+}
+
+int GzipBodyReader::feed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh, const char **text,
+                         size_t *len)
+{
+    *text = nullptr;
+    *len = 0;
+    bool joined = false;
+    if (body_ == GZ_BODY_UNKNOWN || body_ == GZ_BODY_HELD) {
+        body_ = gzip_sniff(tail_.data(), tail_.size(), block, n, finished, fresh);
+        if (body_ == GZ_BODY_HELD) {
+            tail_.append(block, n);
+            return KGX_OK;
+        }
+        joined = body_ == GZ_BODY_TEXT && !tail_.empty();
+    }
+    gzip_ = body_ == GZ_BODY_GZIP;
+    int rc = KGX_OK;
+    if (gzip_) {
+        tail_.append(block, n);
+        rc = inflate(ctx, finished, len);
+        *text = text_;
+    } else if (joined) {
+        joined_.clear();
+        joined_.swap(tail_);
+        joined_.append(block, n);
+        *text = joined_.data();
+        *len = joined_.size();
+    } else {
+        *text = block;
+        *len = n;
+    }
+    if (rc || finished)
+        reset();
+    return rc;
+}
+
+/* the complete members at the front of tail_ into text_ */
+int GzipBodyReader::inflate(kgx_ctx *ctx, bool finished, size_t *len)
+{
+    if (members_ && tail_.size() >= 2 && !((unsigned char)tail_[0] == 0x1f && (unsigned char)tail_[1] == 0x8b))
+        tail_.clear(); /* trailing bytes that are no gzip */
+    uint64_t members = 0, blocked = 0, out_bytes = 0, consumed = 0, out_len = 0;
+    if (int rc = kgx_gunzip_scan(tail_.data(), tail_.size(), finished, &members, &blocked, &out_bytes, &consumed))
+        return rc;
+    /* blocked members state their sizes; a plain member's is found by trying */
+    size_t cap = (size_t)out_bytes + 64;
+    if (members > blocked && finished)
+        cap += 6 * tail_.size() + (size_t(1) << 20);
+    for (;;) {
+        if (cap > text_cap_) {
+            if (text_)
+                kgx_host_free(text_);
+            text_ = nullptr;
+            text_cap_ = 0;
+            void *q = nullptr;
+            if (int rc = kgx_host_alloc(cap, &q))
+                return rc;
+            text_ = static_cast<char *>(q);
+            text_cap_ = cap;
+        }
+        kgx_gunzip_stats gs;
+        const int rc = kgx_gunzip(ctx, tail_.data(), tail_.size(), finished, text_, text_cap_, &out_len, &consumed, &gs);
+        if (rc == KGX_ERANGE && members > blocked) {
+            cap = text_cap_ * 2;
+            continue;
+        }
+        if (rc)
+            return rc;
+        members_ += gs.members;
+        break;
+    }
+    tail_.erase(0, (size_t)consumed);
+    *len = (size_t)out_len;
+    return KGX_OK;
+}
+
+}  // namespace kgx

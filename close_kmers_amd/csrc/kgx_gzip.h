@@ -196,3 +196,63 @@ inline InflateResult gzip_member_inflate(const uint8_t *in, const uint8_t *in_en
 }
 
 }  // namespace kgx
+
+/* ---- the front end of a body that may be gzip (kgx_gunzip.cpp) ------------ */
+
+struct kgx_ctx;
+
+namespace kgx {
+
+enum GzipBody { GZ_BODY_UNKNOWN, GZ_BODY_HELD, GZ_BODY_TEXT, GZ_BODY_GZIP };
+
+/* The sniff at the start of a body (`fresh`: its parser in the start state
+ * with nothing carried), over the bytes held so far followed by the new
+ * block: 1f 8b 08 makes the whole body gzip; a start shorter than gzip's
+ * fixed header (10 bytes) that may still be one is held until more arrives
+ * or the body ends.  Text pays the sniff and nothing else. */
+inline GzipBody gzip_sniff(const char *held, size_t n_held, const char *block, size_t n, bool finished, bool fresh)
+{
+    auto byte = [&](size_t i) { return (unsigned char)(i < n_held ? held[i] : block[i - n_held]); };
+    const size_t have = n_held + n;
+    if (!fresh || have == 0 || byte(0) != 0x1f)
+        return GZ_BODY_TEXT;
+    if (have < 3)
+        return finished ? GZ_BODY_TEXT : GZ_BODY_HELD;
+    if (byte(1) != 0x8b || byte(2) != 8)
+        return GZ_BODY_TEXT;
+    return have < 10 && !finished ? GZ_BODY_HELD : GZ_BODY_GZIP;
+}
+
+/* A body arriving in blocks, as text: the sniff, then either the caller's own
+ * bytes (a text body; the held start and the block joined if bytes were
+ * held) or the text of the block's complete gzip members, inflated on ctx
+ * (kgx_gunzip) into pinned memory (kgx_host_alloc).  A plain (non-blocked)
+ * member is held until the body's last block.  Trailing bytes after a member
+ * that are no gzip are ignored, as gzip does.  The body ends with its last
+ * block or with an error: the next feed() starts one. */
+class GzipBodyReader {
+public:
+    GzipBodyReader() = default;
+    GzipBodyReader(const GzipBodyReader &) = delete;
+    GzipBodyReader &operator=(const GzipBodyReader &) = delete;
+    ~GzipBodyReader();
+    /* one block; `fresh` matters only while the body's kind is undecided.
+     * KGX_OK with *text = null: the bytes are held, nothing to process yet;
+     * else *text, *len (valid until the next call) and gzip() describe them */
+    int feed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh, const char **text, size_t *len);
+    void reset();
+    GzipBody body() const { return body_; }
+    bool gzip() const { return gzip_; } /* the text of the last feed() was inflated */
+
+private:
+    int inflate(kgx_ctx *ctx, bool finished, size_t *len);
+    GzipBody body_ = GZ_BODY_UNKNOWN; /* of the body in progress */
+    bool gzip_ = false;
+    std::string tail_;     /* held first bytes / compressed bytes not consumed yet */
+    std::string joined_;   /* held bytes that were text after all, and the block */
+    uint64_t members_ = 0; /* members inflated so far in this body */
+    char *text_ = nullptr; /* inflated text, pinned */
+    size_t text_cap_ = 0;
+};
+
+}  // namespace kgx

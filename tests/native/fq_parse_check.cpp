@@ -8,6 +8,12 @@
  * exactly its size (so a sanitizer build sees any read past a block), and
  * prints one line per record, "R<TAB>id<TAB>bases", then for the strict parser
  * "E<TAB>line<TAB>id<TAB>report" if it met an error.
+ *
+ *     fq_parse_check sniff HELD BLOCK FINISHED FRESH [HELD BLOCK FINISHED FRESH ...]
+ *
+ * prints gzip_sniff's decision (csrc/kgx_gzip.h) for each case, one word per
+ * line; HELD and BLOCK are bytes in hex ("-" for none), FINISHED and FRESH 0
+ * or 1.  The bytes are copied into buffers of exactly their size.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -17,11 +23,38 @@
 #include <memory>
 
 #include "kgx_fq_parse.h"
+#include "kgx_gzip.h"
+
+static std::unique_ptr<char[]> from_hex(const std::string &hex, size_t *n)
+{
+    *n = hex == "-" ? 0 : hex.size() / 2;
+    std::unique_ptr<char[]> buf(new char[*n]);
+    for (size_t i = 0; i < *n; i++)
+        buf[i] = (char)std::stoi(hex.substr(2 * i, 2), nullptr, 16);
+    return buf;
+}
+
+static int sniff_cases(int argc, char **argv)
+{
+    static const char *const names[] = {"UNKNOWN", "HELD", "TEXT", "GZIP"};
+    if ((argc - 2) % 4)
+        return 2;
+    for (int i = 2; i < argc; i += 4) {
+        size_t n_held, n;
+        const auto held = from_hex(argv[i], &n_held), block = from_hex(argv[i + 1], &n);
+        std::cout << names[kgx::gzip_sniff(held.get(), n_held, block.get(), n, std::atoi(argv[i + 2]) != 0,
+                                           std::atoi(argv[i + 3]) != 0)]
+                  << "\n";
+    }
+    return 0;
+}
 
 int main(int argc, char **argv)
 {
+    if (argc >= 2 && std::string(argv[1]) == "sniff")
+        return sniff_cases(argc, argv);
     if (argc != 4) {
-        std::fprintf(stderr, "usage: fq_parse_check FILE BLOCK strict|handler\n");
+        std::fprintf(stderr, "usage: fq_parse_check FILE BLOCK strict|handler | sniff CASES...\n");
         return 2;
     }
     std::ifstream in(argv[1], std::ios::binary);

@@ -2,7 +2,8 @@
 the oracle's fragments, the stop-at-error FASTQ parser (csrc/kgx_fq_parse.h)
 against the restatement through tests/native/fq_parse_check.cpp -- built with
 the address and undefined-behaviour sanitizers and run directly -- the fq
-handler's parser on the same malformed inputs, and the command line.  No GPU."""
+handler's parser on the same malformed inputs, the text-or-gzip sniff of
+csrc/kgx_gzip.h through the same program, and the command line.  No GPU."""
 import os
 import subprocess
 
@@ -65,7 +66,7 @@ def test_restatement_worked_cases(oracle_lib, frame):
 
 def _build_check():
     from close_kmers_amd import build as kbuild
-    deps = [SRC, os.path.join(kbuild.CSRC, "kgx_fq_parse.h")]
+    deps = [SRC] + [os.path.join(kbuild.CSRC, h) for h in ("kgx_fq_parse.h", "kgx_gzip.h", "kgx_inflate.h")]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
@@ -155,6 +156,48 @@ def test_handler_parser_still_parses_past_errors(tmp_path, name):
         assert [r[0] for r in want] == [b"r1", b"r2", b"r3", b"r5"]
     if name == "bad_character_in_third":
         assert want[2] == (b"r3", b"GGGCCAAATTT")
+
+
+_GZ = bytes([0x1f, 0x8b, 0x08])
+# (the body's first bytes, finished, fresh) -> the sniff's decision, by the
+# rules of the fq handler and fastq_to_protein: a first byte other than 1f, an
+# empty body or a parser not at a fresh start is text; 1f 8b 08 is gzip, but
+# with fewer than gzip's 10 header bytes it is held while more may come; fewer
+# than 3 bytes starting with 1f are held while more may come, text otherwise
+SNIFF_CASES = [
+    (b"", 0, 1, "TEXT"), (b"", 1, 1, "TEXT"),
+    (b"\x1f", 0, 1, "HELD"), (b"\x1f", 1, 1, "TEXT"),
+    (b"\x1f\x8b", 0, 1, "HELD"), (b"\x1f\x8b", 1, 1, "TEXT"),
+    (b"\x1f\x8c", 0, 1, "HELD"), (b"\x1f\x8c", 1, 1, "TEXT"),
+    (_GZ, 0, 1, "HELD"), (_GZ, 1, 1, "GZIP"),
+    (_GZ + bytes(1), 0, 1, "HELD"), (_GZ + bytes(1), 1, 1, "GZIP"),
+    (_GZ + bytes(2), 0, 1, "HELD"), (_GZ + bytes(2), 1, 1, "GZIP"),
+    (_GZ + bytes(3), 0, 1, "HELD"), (_GZ + bytes(3), 1, 1, "GZIP"),
+    (_GZ + bytes(4), 0, 1, "HELD"), (_GZ + bytes(4), 1, 1, "GZIP"),
+    (_GZ + bytes(5), 0, 1, "HELD"), (_GZ + bytes(5), 1, 1, "GZIP"),
+    (_GZ + bytes(6), 0, 1, "HELD"), (_GZ + bytes(6), 1, 1, "GZIP"),
+    (_GZ + bytes(7), 0, 1, "GZIP"), (_GZ + bytes(7), 1, 1, "GZIP"),
+    (_GZ + bytes(9), 0, 1, "GZIP"), (_GZ + bytes(9), 1, 1, "GZIP"),
+    (b"\x1f\x8b\x07", 0, 1, "TEXT"), (b"\x1f\x8b\x07", 1, 1, "TEXT"),
+    (b"\x1f\x8b\x07" + bytes(7), 0, 1, "TEXT"), (b"\x1f\x8c\x08" + bytes(7), 1, 1, "TEXT"),
+    (b"@r1\nACGT\n+\nIIII\n", 0, 1, "TEXT"), (b"@", 0, 1, "TEXT"), (b"@r1\nACGT\n+\nIIII\n", 1, 1, "TEXT"),
+    (b"\x1f", 0, 0, "TEXT"), (_GZ, 0, 0, "TEXT"), (_GZ + bytes(7), 0, 0, "TEXT"), (_GZ + bytes(7), 1, 0, "TEXT"),
+]
+
+
+def test_gzip_sniff_decisions():
+    """gzip_sniff (csrc/kgx_gzip.h), the one sniff of the fq handler and
+    fastq_to_protein: the table above, with the bytes split between the held
+    start and the new block at every position."""
+    args, want = [], []
+    for data, finished, fresh, decision in SNIFF_CASES:
+        for cut in range(len(data) + 1):
+            args += [data[:cut].hex() or "-", data[cut:].hex() or "-", str(finished), str(fresh)]
+            want.append(decision)
+    r = subprocess.run([_build_check(), "sniff"] + args, capture_output=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.decode().split() == want
+    assert {"HELD", "TEXT", "GZIP"} == set(want)
 
 
 def test_command_line_parsing():

@@ -122,6 +122,26 @@ def test_fq_handler_c_abi_matches_golden(gpu, oracle_lib):
         assert out == want
 
 
+def test_fq_handler_with_families_in_parts_matches_golden(gpu, oracle_lib, monkeypatch):
+    """The golden fq data set with its family DB through the multi-part
+    rotation (parts of 4 KiB, the minimum): one block and one FamilyMapper
+    either way, so the text is the reference's."""
+    import os
+    from close_kmers_amd import image_files
+    from helpers import GOLDEN
+    d = os.path.join(GOLDEN, "fq")
+    files = {k: os.path.join(d, v) for k, v in
+             {"genus": "genus.map", "families": "families.tsv", "nr": "nr.fasta"}.items()}
+    want = open(os.path.join(d, "expected_fq_default.txt"), "rb").read()
+    fastq = open(os.path.join(d, "input.fasta"), "rb").read()
+    assert len(fastq) // 4096 >= 2  # more than one part is cut
+    table = image_files.read_image(os.path.join(d, "data"))
+    monkeypatch.setenv("KGX_FQ_PART_KB", "4")
+    with gpu.Image.from_table(table) as img:
+        with gpu.FqHandler(img, os.path.join(d, "data"), **files) as fq:
+            assert fq.process(fastq, True) == want
+
+
 def test_fq_handler_without_families_matches_oracle(gpu, oracle_lib):
     """No family DB: reads without calls are skipped on the host (fast path);
     the output must still equal the oracle's."""

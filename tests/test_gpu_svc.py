@@ -204,7 +204,7 @@ def test_svc_stall_is_replaced_without_blocking(gpu, oracle_lib, monkeypatch):
         monkeypatch.delenv("KGX_SVC_TEST_DROP")
         leaked = img.svc_stat("leaked")
         t0 = time.time()
-        img.svc_stop()  # the facade's replacement (kguts_hip.cpp, process_aa_seq)
+        img.svc_stop()  # the facade's replacement (csrc/kguts_hip.cpp, KmerGuts::process_aa_seq)
         assert time.time() - t0 < 3 and img.svc_stat("leaked") == leaked
         got = ctx.process_batch(np.frombuffer(seqs[0], np.uint8).copy(), np.array([0, len(seqs[0])], np.uint64),
                                 want=3)  # the batch path for the stalled call
