@@ -1063,6 +1063,7 @@ int process_batch_chunked(kgx_ctx *c, const kgx_params *params, const char *resi
     t->opt.probe_serialize = c->opt.probe_serialize;
     t->opt.score_variant = c->opt.score_variant;
     t->opt.score_wave_tiles = c->opt.score_wave_tiles;
+    t->opt.score_lean = c->opt.score_lean;
     kgx_ctx *xs[2] = {c, t};
     if (!c->copy_stream)
         HIP_TRY(own_queue_stream(c->img->device, &c->copy_stream));

@@ -236,6 +236,10 @@ hipError_t launch_filter_build(const void *table, int layout, uint64_t num_sigs,
  * which the wave-parallel scorer takes; SCORE_WAVE (1): the wave scorer for
  * every sequence up to RUN_CAP windows; SCORE_LANE (2): the lane machine
  * only.  The wave scorer needs order_constraint 0 (else: the lane machine).
+ * lean (option score_lean): without KGX_WANT_OTU and under order_constraint 0
+ * the lane machine runs as score_lean_kernel, 1 = fewer registers, 2 = and
+ * its working lanes packed; 0 = score_kernel always.  *lean_taken: whether
+ * score_lean_kernel was launched.
  * plan_status[1] = the batch's longest sequence in windows (launch_plan). */
 enum { SCORE_HYBRID = 0, SCORE_WAVE = 1, SCORE_LANE = 2, SCORE_WAVE_ONLY = 3 /* internal: no sequence > RUN_CAP */ };
 constexpr uint32_t LONG_SEQ = 2048;
@@ -243,7 +247,7 @@ hipError_t launch_score(uint32_t n_seq, uint64_t n_residues, const uint64_t *wba
                         uint64_t max_tiles, const uint64_t *hit_mask, uint32_t tile_windows, uint4 *hot,
                         kgx_call *calls, void *ranges, uint32_t *hit_count, uint32_t *call_count,
                         kgx_params params, uint32_t want, uint32_t hit_format, int variant, uint32_t wave_tiles,
-                        const uint32_t *plan_status, hipStream_t stream);
+                        int lean, const uint32_t *plan_status, hipStream_t stream, bool *lean_taken = nullptr);
 /* find_best_call per sequence: calls[start[s] ..+ count[s]), ws same extent */
 hipError_t launch_best_calls(uint32_t n_seq, const kgx_call *calls, const uint64_t *start, const uint32_t *count,
                              kgx_call *ws, kgx_best_call *out, hipStream_t stream);

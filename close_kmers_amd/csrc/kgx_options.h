@@ -32,6 +32,11 @@ struct CtxOptions {
     int64_t plan_fused = 0;        /* 0 = three kernels, 1 = one look-back launch, 2 = one workgroup */
     int64_t score_variant = 0;     /* 0 = hybrid, 1 = wave-parallel, 2 = lane only (kgx_internal.h) */
     int64_t score_wave_tiles = 16; /* probe tiles of windows per scorer wave */
+    /* the lane scorer for calls without OTU output under order_constraint 0:
+     * 0 = the general kernel, 1 = the lean one (at most 64 VGPRs beside the
+     * probe), 2 = lean with its working lanes packed into whole waves (no
+     * faster than 1 at C2: 0.4574 against 0.4576 ms per step, r17) */
+    int64_t score_lean = 1;
     /* fq fragments (kgx_fq.hip) */
     int64_t fq_residues = 1; /* 1: kgx_fq_fragments writes residues; 0: anchors (kgx_fq_run_device) */
     int64_t fq_count = 1;    /* fq count pass: 1 = lane-per-read stop scan, 0 = wave-per-read translation */
@@ -168,10 +173,12 @@ static const CtxOptionRow CTX_OPTION_TABLE[] = {
     {KGX_OPT(probe_j), 0, 0, "1, 2, 3, 4, 5 or 8", probe_j_ok},
 };
 constexpr size_t CTX_OPTION_COUNT = sizeof(CTX_OPTION_TABLE) / sizeof(CTX_OPTION_TABLE[0]);
-/* options outside the lookup path: the table above is the one that
- * tests/native/options_check.cpp holds against its own record name by name */
-static const CtxOptionRow CTX_OPTION_TABLE_IO[] = {
+/* options declared since, of whatever subsystem: the table above is the one
+ * that tests/native/options_check.cpp holds against its own record name by
+ * name (score_lean's values and text: tests/test_gpu_score_lean.py) */
+static const CtxOptionRow CTX_OPTION_TABLE_LATER[] = {
     {KGX_OPT(gunzip_device), 0, 1, "0 or 1", nullptr},
+    {KGX_OPT(score_lean), 0, 2, "0, 1 or 2", nullptr},
 };
 #undef KGX_OPT
 
@@ -180,7 +187,7 @@ inline const CtxOptionRow *ctx_option_find(const char *name)
     for (const CtxOptionRow &r : CTX_OPTION_TABLE)
         if (!std::strcmp(r.name, name))
             return &r;
-    for (const CtxOptionRow &r : CTX_OPTION_TABLE_IO)
+    for (const CtxOptionRow &r : CTX_OPTION_TABLE_LATER)
         if (!std::strcmp(r.name, name))
             return &r;
     return nullptr;

@@ -533,6 +533,7 @@ struct kgx_ctx {
     uint64_t stream_fallbacks = 0; /* batches rerun exact after a region overflowed */
     bool one_pass_pinned = false; /* the enqueued one-pass batch reads caller-pinned residues */
     uint64_t pinned_batches = 0, nul_reruns = 0;
+    uint64_t lean_scores = 0; /* score stages that launched score_lean_kernel */
     uint32_t counts_enqueued = 0; /* want + 1 of an enqueued collect_counts_enqueue, else 0 */
     kgx::PinnedVec<uint32_t> h_nul;
     std::vector<hipEvent_t> chunk_h2d; /* per chunk: its staged residues are on the device */

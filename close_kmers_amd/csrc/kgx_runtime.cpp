@@ -951,10 +951,21 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
         if (*g)
             gunzip_device = *g == '1';
     }
+    /* KGX_SCORE_LEAN=0|1|2: the default of option "score_lean" for new
+     * contexts (alternated-process A/Bs) */
+    int64_t score_lean = CtxOptions{}.score_lean;
+    if (const char *l = std::getenv("KGX_SCORE_LEAN")) {
+        if (*l && std::strcmp(l, "0") && std::strcmp(l, "1") && std::strcmp(l, "2"))
+            return fail(KGX_EINVAL, std::string("KGX_SCORE_LEAN: 0 (general lane scorer), 1 (lean) or 2 (lean, "
+                                                "packed), not \"") + l + "\"");
+        if (*l)
+            score_lean = *l - '0';
+    }
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
     c->probe_defer = probe_defer;
     c->opt.gunzip_device = gunzip_device;
+    c->opt.score_lean = score_lean;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -1286,11 +1297,14 @@ int kgx_stage_score(kgx_ctx *c, const kgx_params *params, uint32_t want)
         kgx_params_default(&p);
     HIP_TRY(hipSetDevice(c->img->device));
     const bool best = (want & KGX_WANT_BEST) != 0;
+    bool lean_taken = false;
     HIP_TRY(launch_score(c->n_seq, c->n_residues, c->wbase.as<uint64_t>(), c->tile_seq.as<uint32_t>(), c->max_tiles,
                          c->hit_mask.as<uint64_t>(), c->tile_windows, c->hits.as<uint4>(), c->calls.as<kgx_call>(),
                          c->ranges.p, c->hit_count.as<uint32_t>(), c->call_count.as<uint32_t>(), p,
                          want | (best ? KGX_WANT_CALLS : 0u), c->hit_format, c->opt.score_variant,
-                         (uint32_t)c->opt.score_wave_tiles, c->plan_status.as<uint32_t>(), c->stream));
+                         (uint32_t)c->opt.score_wave_tiles, (int)c->opt.score_lean, c->plan_status.as<uint32_t>(),
+                         c->stream, &lean_taken));
+    c->lean_scores += lean_taken;
     c->have_best = false;
     c->have_otus = false;
     if (want & KGX_WANT_OTU) {
@@ -1456,6 +1470,8 @@ int kgx_ctx_stat(kgx_ctx *c, const char *name, int64_t *value)
         *value = (int64_t)c->pinned_batches;
     else if (n == "nul_reruns")
         *value = (int64_t)c->nul_reruns;
+    else if (n == "lean_scores")
+        *value = (int64_t)c->lean_scores;
     else
         return fail(KGX_EINVAL, "unknown statistic " + n);
     return KGX_OK;

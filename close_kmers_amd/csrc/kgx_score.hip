@@ -12,6 +12,8 @@
 #include "kgx_device.h"
 #include "kgx_lstd.h"
 
+#include <type_traits>
+
 namespace kgx {
 
 /* ------------------------------------------------------------------------ */
@@ -59,6 +61,41 @@ __device__ __forceinline__ uint32_t for_each_run(const uint64_t *__restrict__ hi
     return ordinal;
 }
 
+/*
+ * The same walk for the lean scorer, whose caller knows that the batch's hit
+ * slots (and so its windows) stay below 2^32: 32-bit indices, one running
+ * slot index instead of tile and count, and the next mask word not loaded
+ * ahead (it would hold two more registers across f).  Same arguments to f.
+ */
+template <class F>
+__device__ __forceinline__ uint32_t for_each_run_lean(const uint64_t *__restrict__ hit_mask,
+                                                      uint32_t tile_windows, uint32_t gw0, uint32_t gw1,
+                                                      F &&f)
+{
+    if (gw0 >= gw1)
+        return 0;
+    const uint32_t J = tile_windows / 64;
+    const uint32_t gfirst = gw0 >> 6, glast = (gw1 - 1) >> 6;
+    uint32_t slot = gfirst / J * tile_windows; /* storage slot of the first hit of word g */
+    for (uint32_t g = gfirst / J * J; g < gfirst; g++)
+        slot += (uint32_t)__popcll(hit_mask[g]);
+    uint32_t ordinal = 0;
+    for (uint32_t g = gfirst; g <= glast; g++) {
+        if (g != gfirst && g % J == 0)
+            slot = g / J * tile_windows;
+        const uint64_t full = hit_mask[g];
+        const uint32_t lo = g == gfirst ? (gw0 & 63) : 0u;
+        const uint32_t hi = g == glast ? ((gw1 - 1) & 63) + 1 : 64u;
+        const uint64_t bits = full & bit_range(lo, hi);
+        const uint32_t cnt = (uint32_t)__popcll(bits);
+        if (cnt)
+            f(slot + (uint32_t)__popcll(full & bit_range(0, lo)), cnt, ordinal, bits, 64 * g - gw0);
+        ordinal += cnt;
+        slot += (uint32_t)__popcll(full);
+    }
+    return ordinal;
+}
+
 /* ------------------------------------------------------------------------ */
 /* score                                                                     */
 /* ------------------------------------------------------------------------ */
@@ -90,48 +127,91 @@ struct RunTail {
 };
 
 constexpr int SCORE_BATCH = 8; /* records per load batch (double-buffered); 2 for short sequences */
+constexpr int SCORE_LEAN_BATCH = 4; /* the same of the lean form */
 
-template <bool PK, int SB = SCORE_BATCH>
-__device__ __forceinline__ void score_sequence(
+/* The lean form reads of a record only dwords 1 and 2 (HitFields::fi and
+ * ::wt, the same dwords in both hit formats) as one 8-byte load at a 4-byte
+ * boundary; the general form reads the record whole. */
+struct __attribute__((packed, aligned(4))) HitYZ {
+    uint32_t y, z;
+};
+__device__ __forceinline__ uint2 load_yz(const uint4 *rec)
+{
+    const HitYZ v = *reinterpret_cast<const HitYZ *>(reinterpret_cast<const uint32_t *>(rec) + 1);
+    return make_uint2(v.y, v.z);
+}
+__device__ __forceinline__ const uint4 &as_hit(const uint4 &r) { return r; }
+__device__ __forceinline__ uint4 as_hit(const uint2 &r) { return make_uint4(0u, r.x, r.y, 0u); }
+
+/*
+ * LEAN: calls only, order_constraint 0 (launch_score's choice).  The fields
+ * that only the OTU flags, the ranges and the order constraint read -- a
+ * hit's ordinal, storage slot, flag dword and avg, run_start, last_idx -- are
+ * then dead and the compiler drops them; the records in flight are (y, z)
+ * pairs, and the mask words are walked by for_each_run_lean (32-bit indices,
+ * no read-ahead).  The run rules below are written once for both forms; the
+ * general form compiles to the instructions it had before the lean one was
+ * split off (tools/asm_compare.py), which is why its record load and its
+ * walker are spelled out beside the lean ones and not behind a common helper.
+ * The function has two parts, the early-out test (EARLY), made from mask
+ * words alone, and the runs (RUNS); score_lean_kernel calls them apart.
+ * Returns false when the sequence left at the early-out (its counts are
+ * written), true otherwise.
+ */
+template <bool PK, int SB = SCORE_BATCH, bool LEAN = false, bool EARLY = true, bool RUNS = true>
+__device__ __forceinline__ bool score_sequence(
     uint32_t s, const uint64_t *__restrict__ wbase, const uint64_t *__restrict__ hit_mask,
     uint32_t tile_windows, uint4 *__restrict__ hot, kgx_call *__restrict__ calls,
     uint2 *__restrict__ ranges, uint32_t *__restrict__ hit_count, uint32_t *__restrict__ call_count,
     const kgx_params &prm, uint32_t want)
 {
-    const uint64_t gw0 = wbase[s], gw1 = wbase[s + 1];
-    const bool want_calls = (want & KGX_WANT_CALLS) != 0;
-    const bool want_otu = (want & KGX_WANT_OTU) != 0;
-    if (!want_calls && !want_otu) {
-        /* process_set_of_hits returns before doing anything (kguts.cc:737) */
-        hit_count[s] = for_each_run(hit_mask, tile_windows, gw0, gw1,
-                                    [](uint64_t, uint32_t, uint32_t, uint64_t, uint32_t) {});
-        call_count[s] = 0;
-        return;
-    }
-    if (!want_otu && prm.min_hits > 0 && gw1 > gw0) {
-        /* fewer hits than min_hits: no run can reach a call (a call counts
-         * at most the sequence's hits, kguts.cc:757-770), and without OTU
-         * output the run flags are not kept -- count and leave without
-         * reading a record (fq fragments: ~16 windows, < 1 hit each) */
-        uint32_t nh = 0;
-        for (uint64_t g = gw0 >> 6; g <= (gw1 - 1) >> 6; g++) {
-            const uint32_t lo = g == (gw0 >> 6) ? (uint32_t)(gw0 & 63) : 0u;
-            const uint32_t hi = g == ((gw1 - 1) >> 6) ? (uint32_t)((gw1 - 1) & 63) + 1 : 64u;
-            nh += (uint32_t)__popcll(hit_mask[g] & bit_range(lo, hi));
-        }
-        if ((int)nh < prm.min_hits) {
-            hit_count[s] = nh;
+    /* LEAN: launch_score has seen that the hit slots stay below 2^32 */
+    typedef typename std::conditional<LEAN, uint32_t, uint64_t>::type Idx;
+    const Idx gw0 = (Idx)wbase[s], gw1 = (Idx)wbase[s + 1];
+    auto each_run = [&](auto &&f) {
+        if constexpr (LEAN)
+            return for_each_run_lean(hit_mask, tile_windows, gw0, gw1, f);
+        else
+            return for_each_run(hit_mask, tile_windows, gw0, gw1, f);
+    };
+    /* LEAN: launch_score sends only requests for calls without OTU output */
+    const bool want_calls = LEAN || (want & KGX_WANT_CALLS) != 0;
+    const bool want_otu = !LEAN && (want & KGX_WANT_OTU) != 0;
+    if (EARLY) {
+        if (!want_calls && !want_otu) {
+            /* process_set_of_hits returns before doing anything (kguts.cc:737) */
+            hit_count[s] = each_run([](Idx, uint32_t, uint32_t, uint64_t, uint32_t) {});
             call_count[s] = 0;
-            return;
+            return false;
+        }
+        if (!want_otu && prm.min_hits > 0 && gw1 > gw0) {
+            /* fewer hits than min_hits: no run can reach a call (a call counts
+             * at most the sequence's hits, kguts.cc:757-770), and without OTU
+             * output the run flags are not kept -- count and leave without
+             * reading a record (fq fragments: ~16 windows, < 1 hit each) */
+            uint32_t nh = 0;
+            for (Idx g = gw0 >> 6; g <= (gw1 - 1) >> 6; g++) {
+                const uint32_t lo = g == (gw0 >> 6) ? (uint32_t)(gw0 & 63) : 0u;
+                const uint32_t hi = g == ((gw1 - 1) >> 6) ? (uint32_t)((gw1 - 1) & 63) + 1 : 64u;
+                nh += (uint32_t)__popcll(hit_mask[g] & bit_range(lo, hi));
+            }
+            if ((int)nh < prm.min_hits) {
+                hit_count[s] = nh;
+                call_count[s] = 0;
+                return false;
+            }
         }
     }
+    if (!RUNS)
+        return true;
+    typedef typename std::conditional<LEAN, uint2, uint4>::type Rec;
 
     typedef HitFields<PK> HF;
     constexpr uint32_t F_RUN = KGX_HIT_IN_RUN << HF::FLAG_SHIFT, F_CNT = KGX_HIT_COUNTED << HF::FLAG_SHIFT,
                        F_OTU = KGX_HIT_OTU << HF::FLAG_SHIFT;
     constexpr int FD = HF::FLAG_DWORD;
     uint32_t *hw = reinterpret_cast<uint32_t *>(hot); /* 4 dwords per hit, flags in dword FD */
-    const uint64_t cbase = gw0; /* calls / ranges of s live at [gw0, ...) */
+    const Idx cbase = gw0; /* calls / ranges of s live at [gw0, ...) */
     const uint32_t gap = (uint32_t)prm.max_gap;
     int n = 0;
     uint32_t cur = 0, first_pos = 0, last_pos = 0, last_idx = 0, run_start = 0;
@@ -176,7 +256,8 @@ __device__ __forceinline__ void score_sequence(
         }
     };
 
-    auto step = [&](const uint4 &r, uint32_t i, uint64_t at, uint32_t pos) {
+    auto step = [&](const Rec &rec, uint32_t i, Idx at, uint32_t pos) {
+        const auto &r = as_hit(rec);
         const uint32_t avg = HF::avg(r);
         const uint32_t fI = HF::fi(r);
         const float wt = __uint_as_float(HF::wt(r));
@@ -196,7 +277,7 @@ __device__ __forceinline__ void score_sequence(
             first_pos = pos;
         }
         bool accept = true;
-        if (prm.order_constraint && n > 0) { /* kguts.cc:838-842 */
+        if (!LEAN && prm.order_constraint && n > 0) { /* kguts.cc:838-842 */
             const uint32_t d = (pos - p1.pos) - (uint32_t)((int)p1.avg - (int)avg);
             accept = (fI == p1.fI) && d <= 20u;
         }
@@ -224,15 +305,19 @@ __device__ __forceinline__ void score_sequence(
     /* hits are read SB at a time and double-buffered: batch b+1's
      * loads are in flight while batch b runs through the state machine (the
      * machine is serial, its inputs are not) */
-    auto load_batch = [&](uint4 *rb, uint64_t at0, uint32_t b, uint32_t c) {
+    auto load_batch = [&](Rec *rb, Idx at0, uint32_t b, uint32_t c) {
 #pragma unroll
         for (int k = 0; k < SB; k++)
-            if (b + k < c)
-                rb[k] = hot[at0 + b + k];
+            if (b + k < c) {
+                if constexpr (LEAN)
+                    rb[k] = load_yz(hot + (at0 + b + k));
+                else
+                    rb[k] = hot[at0 + b + k];
+            }
     };
-    const uint32_t nh = for_each_run(hit_mask, tile_windows, gw0, gw1,
-                                     [&](uint64_t at0, uint32_t c, uint32_t ord0, uint64_t bits, uint32_t pbase) {
-        uint4 ra[SB], rb[SB];
+    const uint32_t nh = each_run(
+                                     [&](Idx at0, uint32_t c, uint32_t ord0, uint64_t bits, uint32_t pbase) {
+        Rec ra[SB], rb[SB];
         load_batch(ra, at0, 0, c);
         for (uint32_t b = 0; b < c; b += 2 * SB) {
             if (b + SB < c)
@@ -268,7 +353,7 @@ __device__ __forceinline__ void score_sequence(
         uint2 rg = ranges[cbase];
         const uint32_t end = ranges[cbase + ncalls - 1].y;
         for_each_run(hit_mask, tile_windows, gw0, gw1,
-                     [&](uint64_t at0, uint32_t c, uint32_t ord0, uint64_t, uint32_t) {
+                     [&](Idx at0, uint32_t c, uint32_t ord0, uint64_t, uint32_t) {
             for (uint32_t k = 0; k < c; k++) {
                 const uint32_t i = ord0 + k;
                 if (i > end)
@@ -283,6 +368,7 @@ __device__ __forceinline__ void score_sequence(
             }
         });
     }
+    return true;
 }
 
 /* skip_above: sequences with windows in (skip_above, RUN_CAP] are the wave
@@ -302,6 +388,60 @@ __global__ __launch_bounds__(256) void score_kernel(
             continue;
         score_sequence<PK, SB>(s, wbase, hit_mask, tile_windows, hot, calls, ranges, hit_count, call_count, prm,
                                want);
+    }
+}
+
+/*
+ * The lean lane scorer (score_sequence<.., LEAN>: calls without OTU output,
+ * order_constraint 0), one workgroup per 256 sequences.  Every lane makes the
+ * early-out test for its own sequence from the mask words.  PACK: the
+ * sequences that stay are then listed in LDS in block order -- a ballot and
+ * lanes_below per wave, four wave totals -- and after one barrier lane i
+ * scores the i-th of them, so the lanes that work fill whole waves and a wave
+ * left with nothing returns its registers at once.  Each sequence's results
+ * go to its own slots as in score_kernel.  When every lane stays (min_hits
+ * <= 0) lane i finds its own sequence again: the packing costs the barrier.
+ */
+template <bool PK, int SB, bool PACK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_lean_kernel(
+    uint32_t n_seq, const uint64_t *__restrict__ wbase, const uint64_t *__restrict__ hit_mask,
+    uint32_t tile_windows, uint4 *__restrict__ hot, kgx_call *__restrict__ calls,
+    uint32_t *__restrict__ hit_count, uint32_t *__restrict__ call_count, kgx_params prm, uint32_t want,
+    uint32_t skip_above)
+{
+    __shared__ uint32_t stay_seq[4][64]; /* per wave: its staying sequences, in lane order */
+    __shared__ uint32_t stay_n[4];
+    /* grid-stride by workgroup (KGX_SCORE_GRID_CAP), uniform over the workgroup */
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < n_seq; base += (uint64_t)gridDim.x * 256u) {
+        uint32_t s = (uint32_t)min(base + threadIdx.x, (uint64_t)n_seq);
+        bool stay = false;
+        if (s < n_seq) {
+            const uint64_t w = wbase[s + 1] - wbase[s];
+            stay = !(w > skip_above && w <= (uint64_t)RUN_CAP) &&
+                   score_sequence<PK, SB, true, true, false>(s, wbase, hit_mask, tile_windows, hot, calls, nullptr,
+                                                             hit_count, call_count, prm, want);
+        }
+        if constexpr (PACK) {
+            const uint32_t wave = threadIdx.x >> 6;
+            const uint64_t m = __ballot(stay);
+            if (stay)
+                stay_seq[wave][lanes_below(m)] = s;
+            if (lane_id() == 0)
+                stay_n[wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t i = threadIdx.x, w = 0;
+            while (w < 4 && i >= stay_n[w])
+                i -= stay_n[w++];
+            stay = w < 4;
+            if (stay)
+                s = stay_seq[w][i];
+        }
+        if (stay)
+            score_sequence<PK, SB, true, false, true>(s, wbase, hit_mask, tile_windows, hot, calls, nullptr, hit_count,
+                                                call_count, prm, want);
+        if constexpr (PACK)
+            if (base + (uint64_t)gridDim.x * 256u < n_seq)
+                __syncthreads(); /* the lists are rewritten by the next round */
     }
 }
 
@@ -729,8 +869,10 @@ hipError_t launch_score(uint32_t n_seq, uint64_t n_residues, const uint64_t *wba
                         uint64_t max_tiles, const uint64_t *hit_mask, uint32_t tile_windows, uint4 *hot,
                         kgx_call *calls, void *ranges, uint32_t *hit_count, uint32_t *call_count,
                         kgx_params params, uint32_t want, uint32_t hit_format, int variant, uint32_t wave_tiles,
-                        const uint32_t *plan_status, hipStream_t stream)
+                        int lean, const uint32_t *plan_status, hipStream_t stream, bool *lean_taken)
 {
+    if (lean_taken)
+        *lean_taken = false;
     if (n_seq == 0)
         return hipSuccess;
     const bool pk = hit_format == HIT_PACKED16;
@@ -784,14 +926,35 @@ hipError_t launch_score(uint32_t n_seq, uint64_t n_residues, const uint64_t *wba
 #define KGX_SCORE(P, B)                                                                                          \
     hipLaunchKernelGGL((score_kernel<P, B>), sgrid, dim3(256), 0, stream, n_seq, wbase, hit_mask, tile_windows, hot, \
                        calls, static_cast<uint2 *>(ranges), hit_count, call_count, params, want, skip)
+    /* option score_lean: calls without OTU output under order_constraint 0
+     * (lookup_request's find_best_match) take the lean kernel, 1 = as it is,
+     * 2 = with its working lanes packed; everything else the general one */
+#define KGX_LEAN(P, B, PACK)                                                                                     \
+    hipLaunchKernelGGL((score_lean_kernel<P, B, PACK>), sgrid, dim3(256), 0, stream, n_seq, wbase, hit_mask,     \
+                       tile_windows, hot, calls, hit_count, call_count, params, want, skip)
+#define KGX_LANES(P, B, LB)                                                                                       \
+    do {                                                                                                         \
+        if (lean_ok && lean >= 2)                                                                                \
+            KGX_LEAN(P, LB, true);                                                                               \
+        else if (lean_ok)                                                                                        \
+            KGX_LEAN(P, LB, false);                                                                              \
+        else                                                                                                     \
+            KGX_SCORE(P, B);                                                                                     \
+    } while (0)
+    const bool lean_ok = lean > 0 && (want & KGX_WANT_CALLS) && !(want & KGX_WANT_OTU) && params.order_constraint == 0 &&
+                         max_tiles * tile_windows < (1ull << 32); /* its slot indices are 32-bit */
+    if (lean_taken)
+        *lean_taken = lean_ok;
     if (pk && small)
-        KGX_SCORE(true, 2);
+        KGX_LANES(true, 2, 2);
     else if (pk)
-        KGX_SCORE(true, SCORE_BATCH);
+        KGX_LANES(true, SCORE_BATCH, SCORE_LEAN_BATCH);
     else if (small)
-        KGX_SCORE(false, 2);
+        KGX_LANES(false, 2, 2);
     else
-        KGX_SCORE(false, SCORE_BATCH);
+        KGX_LANES(false, SCORE_BATCH, SCORE_LEAN_BATCH);
+#undef KGX_LANES
+#undef KGX_LEAN
 #undef KGX_SCORE
     if (hybrid) {
         if (pk)

@@ -590,6 +590,15 @@ void *kgx_ctx_stream(kgx_ctx *ctx);
  * hits, serial f32 sums only); 2 = lanes only.  The wave scorer needs
  * order_constraint 0 (else lanes).  Results are identical;
  * "score_wave_tiles" (1..256, default 16) = probe tiles of windows per wave;
+ * "score_lean" (0, 1 or 2, default 1): the lane scorer for calls without
+ * KGX_WANT_OTU under order_constraint 0 (what lookup_request asks for) as a
+ * kernel of its own that reads two dwords of each hit record and holds at
+ * most 64 registers, so that it fits beside the probe wave for wave (1), and
+ * with the lanes whose sequences pass min_hits packed into whole waves of
+ * their workgroup (2: measured no faster than 1, profiles/TRIED.md); 0 = the
+ * general kernel for every request.  Same results with each.  The
+ * environment variable KGX_SCORE_LEAN (0, 1 or 2), read when a context is
+ * created, sets its default for that context;
  * "fq_count" 1 (default) = the fq count pass scans stop codons one lane per
  * read, 0 = it translates like the emit pass (one wave per read);
  * "fq_residues" 1 (default) = kgx_fq_fragments writes the fragments'
@@ -663,7 +672,8 @@ int kgx_ctx_set_option(kgx_ctx *ctx, const char *name, int64_t value);
  * (small host batches that took the one-launch path / the one-wait path),
  * "stream_fallbacks" (streamed batches rerun exact after a region overflow or
  * a NUL in pinned input), "pinned_batches" (streamed batches read straight from
- * the caller's pinned residues), "nul_reruns" */
+ * the caller's pinned residues), "nul_reruns", "lean_scores" (score stages
+ * whose lane scorer was the lean kernel, option "score_lean") */
 int kgx_ctx_stat(kgx_ctx *ctx, const char *name, int64_t *value);
 /* launch on a caller-owned stream instead (hipStream_t; NULL = own stream) */
 int kgx_ctx_set_stream(kgx_ctx *ctx, void *stream);
