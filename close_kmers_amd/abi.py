@@ -205,6 +205,28 @@ class FqText(ctypes.Structure):
                 ("frame", ctypes.c_void_p), ("token", ctypes.c_void_p)]
 
 
+FQ_STRICT, FQ_FINISHED = 1, 2  # KGX_FQ_STRICT, KGX_FQ_FINISHED
+FQ_PARSE_MAX = 0xFFFFF000      # KGX_FQ_PARSE_MAX
+# kgx_fq_reads.error -> the reference's wording (fastq_parser.h:60-135); 3 is followed by the byte and "'"
+FQ_ERROR_TEXT = ("", "Starts with >. Is this a fasta file not a fastq file?", "Missing @", "Bad data character '",
+                 "Missing +")
+
+
+class FqReads(ctypes.Structure):
+    """kgx_fq_reads: the reads of a FASTQ text, framed on the device."""
+    _fields_ = [("n_reads", ctypes.c_uint32), ("n_reads_no_id", ctypes.c_uint32), ("n_bases", ctypes.c_uint64),
+                ("n_id_bytes", ctypes.c_uint64), ("bases", ctypes.c_void_p), ("read_offsets", ctypes.c_void_p),
+                ("ids", ctypes.c_void_p), ("id_offsets", ctypes.c_void_p), ("consumed", ctypes.c_uint64),
+                ("newlines", ctypes.c_uint64), ("error", ctypes.c_uint32), ("error_byte", ctypes.c_uint32),
+                ("error_pos", ctypes.c_uint64), ("error_newlines", ctypes.c_uint64),
+                ("upload_ms", ctypes.c_float), ("parse_ms", ctypes.c_float)]
+
+    def error_text(self) -> str:
+        """The reference's words for the error ("" if none)."""
+        t = FQ_ERROR_TEXT[self.error]
+        return t + chr(self.error_byte) + "'" if self.error == 3 else t
+
+
 class F2pStats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint64) for k in ("reads", "reads_no_id", "fragments", "text_bytes", "parts")] + \
         [("error_line", ctypes.c_uint32), ("gzip", ctypes.c_uint32)] + \
@@ -323,6 +345,9 @@ SIGNATURES = {
     "kgx_fq_fragments_finish": (_INT, [_P, ctypes.POINTER(Fragments)]),
     "kgx_fq_run_device": (_INT, [_P, ctypes.POINTER(Params), ctypes.POINTER(Fragments), _U32, _P]),
     "kgx_fq_proteins": (_INT, [_P, _P, _P, _P, _P, _U32, ctypes.POINTER(FqText)]),
+    "kgx_fq_parse": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
+    "kgx_fq_parse_device": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
+    "kgx_fq_proteins_device": (_INT, [_P, ctypes.POINTER(FqReads), ctypes.POINTER(FqText)]),
     "kgx_f2p_create": (_INT, [_P, _U64, _PP]),
     "kgx_f2p_destroy": (_INT, [_P]),
     "kgx_f2p_process": (_INT, [_P, _CS, _U64, _INT, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_U64)]),
@@ -883,6 +908,36 @@ class Context:
                                     ids.ctypes.data if ids.size else None, ioff.ctypes.data, len(off) - 1,
                                     ctypes.byref(t)), "kgx_fq_proteins")
         return t
+
+    def fq_parse(self, text: bytes, flags: int = 0) -> FqReads:
+        """kgx_fq_parse: host FASTQ text framed on the device, the reads left there."""
+        text = bytes(text)
+        r = FqReads()
+        check(lib().kgx_fq_parse(self.handle, _bytes_ptr(text), len(text), flags, ctypes.byref(r)), "kgx_fq_parse")
+        return r
+
+    def fq_parse_device(self, d_text: int, n: int, flags: int = 0) -> FqReads:
+        """kgx_fq_parse_device: n bytes of FASTQ text in device memory (16-byte aligned)."""
+        r = FqReads()
+        check(lib().kgx_fq_parse_device(self.handle, d_text, n, flags, ctypes.byref(r)), "kgx_fq_parse_device")
+        return r
+
+    def fq_proteins_device(self, reads: FqReads) -> FqText:
+        """kgx_fq_proteins_device: the six-frame FASTA records of the last fq_parse's reads."""
+        t = FqText()
+        check(lib().kgx_fq_proteins_device(self.handle, ctypes.byref(reads), ctypes.byref(t)),
+              "kgx_fq_proteins_device")
+        return t
+
+    def fq_reads_to_host(self, r: FqReads, arrays=("bases", "read_offsets", "ids", "id_offsets")) -> dict:
+        """Host copies of a kgx_fq_reads' arrays (tests / tools)."""
+        out = {"bases": np.zeros(r.n_bases, np.uint8), "read_offsets": np.zeros(r.n_reads + 1, np.uint64),
+               "ids": np.zeros(r.n_id_bytes, np.uint8), "id_offsets": np.zeros(r.n_reads + 1, np.uint64)}
+        out = {k: out[k] for k in arrays}
+        for k, a in out.items():
+            if a.nbytes and getattr(r, k):
+                check(lib().kgx_memcpy_d2h(a.ctypes.data, getattr(r, k), a.nbytes), "d2h")
+        return out
 
     def fq_text_to_host(self, t: FqText) -> dict:
         """Host copies of a kgx_fq_text (tests / tools)."""

@@ -1823,11 +1823,9 @@ struct WidenU32 {
 
 namespace kgx {
 
-/* reads and ids in host memory -> the records on the device (see above) */
-int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
-                const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out)
+/* what both entries do first: the events, the clocks and the result cleared */
+static int fq_proteins_begin(kgx_ctx *c, uint32_t n_reads, kgx_fq_text *out)
 {
-    hipStream_t st = c->stream;
     if (int rc = ensure_events(c->ft_events, 5, hipEventDefault))
         return rc;
     for (float &m : c->ft_ms)
@@ -1835,6 +1833,18 @@ int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, con
     *out = kgx_fq_text{};
     out->n_reads = n_reads;
     c->fq_pend.active = false;
+    return KGX_OK;
+}
+
+static int fq_proteins_run(kgx_ctx *c, uint32_t n_reads, uint64_t n_bases, kgx_fq_text *out);
+
+/* reads and ids in host memory -> the records on the device (see above) */
+int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
+                const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out)
+{
+    hipStream_t st = c->stream;
+    if (int rc = fq_proteins_begin(c, n_reads, out))
+        return rc;
     if (!n_reads)
         return KGX_OK;
     const uint64_t i0 = id_offsets[0], n_id = id_offsets[n_reads] - i0;
@@ -1858,7 +1868,31 @@ int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, con
     if (n_id)
         HIP_TRY(hipMemcpyAsync(c->ft_ids.p, ids + i0, n_id, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(c->ft_events[1], st));
+    return fq_proteins_run(c, n_reads, n_bases, out);
+}
 
+/* reads and ids already in c->fq_bases / fq_roff / ft_ids / ft_idoff, where
+ * kgx_fq_parse left them: no upload */
+int fq_proteins_device(kgx_ctx *c, const kgx_fq_reads *reads, kgx_fq_text *out)
+{
+    if (int rc = fq_proteins_begin(c, reads->n_reads, out))
+        return rc;
+    if (!reads->n_reads)
+        return KGX_OK;
+    if (reads->bases != c->fq_bases.p || reads->read_offsets != c->fq_roff.p || reads->ids != c->ft_ids.p ||
+        reads->id_offsets != c->ft_idoff.p || (reads->n_bases + 16 > c->fq_bases.cap) ||
+        ((uint64_t)reads->n_reads + 1) * 8 > c->fq_roff.cap)
+        return fail(KGX_EINVAL, "kgx_fq_proteins_device: not the reads of this context's last kgx_fq_parse call");
+    c->fq_up.active = false;
+    HIP_TRY(hipEventRecord(c->ft_events[0], c->stream));
+    HIP_TRY(hipEventRecord(c->ft_events[1], c->stream));
+    return fq_proteins_run(c, reads->n_reads, reads->n_bases, out);
+}
+
+/* the kernels over the reads on the device; ft_events[1] is recorded */
+static int fq_proteins_run(kgx_ctx *c, uint32_t n_reads, uint64_t n_bases, kgx_fq_text *out)
+{
+    hipStream_t st = c->stream;
     const uint64_t n_rf = (uint64_t)n_reads * 6;
     const uint32_t n_tiles = (uint32_t)(((uint64_t)n_reads + FQ_TILE - 1) / FQ_TILE);
     const dim3 grid((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG);
@@ -1942,6 +1976,14 @@ int kgx_fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets,
         return fail(KGX_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(c->img->device));
     return fq_proteins(c, bases, read_offsets, ids, id_offsets, n_reads, out);
+}
+
+int kgx_fq_proteins_device(kgx_ctx *c, const kgx_fq_reads *reads, kgx_fq_text *out)
+{
+    if (!c || !reads || !out)
+        return fail(KGX_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->img->device));
+    return fq_proteins_device(c, reads, out);
 }
 
 }  // extern "C"

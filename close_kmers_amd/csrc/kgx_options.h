@@ -113,6 +113,13 @@ struct CtxOptions {
      * 13.1-13.4 against 14.1 at level 1.  This project's own 16 host threads
      * reach 5.8 and 5.1, so a caller that wants throughput sets 1 */
     int64_t gunzip_device = 0;
+    /* kgx_f2p_process: a part's FASTQ text is framed on the device
+     * (kgx_fq_parse, kgx_fq_parse.hip) instead of by the host's strict parser
+     * (kgx_fq_parse.h).  The output is the same bytes.  Measured 2.4 times as
+     * fast for 10M reads (274 against 656 ms, profiles/fq_parse_device_bench.json);
+     * the default stays 0 until that is repeated on a second box (DESIGN.md
+     * §8.12, §12) */
+    int64_t fq_parse_device = 0;
 };
 
 struct CtxOptionRow {
@@ -179,6 +186,7 @@ constexpr size_t CTX_OPTION_COUNT = sizeof(CTX_OPTION_TABLE) / sizeof(CTX_OPTION
 static const CtxOptionRow CTX_OPTION_TABLE_LATER[] = {
     {KGX_OPT(gunzip_device), 0, 1, "0 or 1", nullptr},
     {KGX_OPT(score_lean), 0, 2, "0, 1 or 2", nullptr},
+    {KGX_OPT(fq_parse_device), 0, 1, "0 or 1", nullptr},
 };
 #undef KGX_OPT
 

@@ -322,6 +322,9 @@ int fq_fragments(kgx_ctx *c, const uint8_t *d_bases, const uint64_t *d_read_off,
 /* kgx_fq_proteins behind its argument checks (kgx_fq.hip); the context's device is current */
 int fq_proteins(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, const char *ids,
                 const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out);
+/* kgx_fq_proteins_device behind its argument checks: the reads already sit
+ * in c->fq_bases / fq_roff / ft_ids / ft_idoff (kgx_fq_parse_device) */
+int fq_proteins_device(kgx_ctx *c, const kgx_fq_reads *reads, kgx_fq_text *out);
 /* kgx_stage_probe over fragments left as DNA (launch_probe_dna) */
 int stage_probe_dna(kgx_ctx *c, const uint8_t *bases, uint64_t n_bases, const uint64_t *anchors,
                     const uint64_t *d_off);
@@ -480,6 +483,12 @@ struct kgx_ctx {
     kgx::PinnedVec<uint64_t> h_ft_idoff;
     std::vector<hipEvent_t> ft_events; /* timing: start, uploaded, indexed, sized, written */
     float ft_ms[4] = {0, 0, 0, 0};     /* upload, scan and indices, sizes, write of the last call */
+    /* kgx_fq_parse (kgx_fq_parse.hip): the uploaded text, per tile its state
+     * map, entry state, event counts and their prefix, per lane its entry
+     * state, and the call's sums */
+    kgx::DevBuf fp_text, fp_map, fp_state, fp_lane, fp_cnt, fp_pre, fp_sum;
+    kgx::PinnedVec<uint64_t> h_fp_sum;
+    std::vector<hipEvent_t> fp_events; /* timing: upload start, parse start, parse end */
     /* kgx_gunzip / kgx_gunzip_device (kgx_gunzip.cpp) */
     kgx::DevBuf gz_in, gz_out, gz_members, gz_status, gz_stats;
     kgx::PinnedVec<kgx_gz_member> h_gz_members;
@@ -534,6 +543,7 @@ struct kgx_ctx {
     bool one_pass_pinned = false; /* the enqueued one-pass batch reads caller-pinned residues */
     uint64_t pinned_batches = 0, nul_reruns = 0;
     uint64_t lean_scores = 0; /* score stages that launched score_lean_kernel */
+    uint64_t fq_parses = 0;   /* texts framed on the device (kgx_fq_parse, kgx_fq_parse_device; n > 0) */
     uint32_t counts_enqueued = 0; /* want + 1 of an enqueued collect_counts_enqueue, else 0 */
     kgx::PinnedVec<uint32_t> h_nul;
     std::vector<hipEvent_t> chunk_h2d; /* per chunk: its staged residues are on the device */

@@ -961,11 +961,21 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
         if (*l)
             score_lean = *l - '0';
     }
+    /* KGX_FQ_PARSE_DEVICE=0|1: the default of option "fq_parse_device" for
+     * new contexts (the command line's own context has no other switch) */
+    int64_t fq_parse_device = CtxOptions{}.fq_parse_device;
+    if (const char *p = std::getenv("KGX_FQ_PARSE_DEVICE")) {
+        if (*p && std::strcmp(p, "0") && std::strcmp(p, "1"))
+            return fail(KGX_EINVAL, std::string("KGX_FQ_PARSE_DEVICE: 0 (host parser) or 1 (device), not \"") + p + "\"");
+        if (*p)
+            fq_parse_device = *p == '1';
+    }
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
     c->probe_defer = probe_defer;
     c->opt.gunzip_device = gunzip_device;
     c->opt.score_lean = score_lean;
+    c->opt.fq_parse_device = fq_parse_device;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -1472,6 +1482,8 @@ int kgx_ctx_stat(kgx_ctx *c, const char *name, int64_t *value)
         *value = (int64_t)c->nul_reruns;
     else if (n == "lean_scores")
         *value = (int64_t)c->lean_scores;
+    else if (n == "fq_parses")
+        *value = (int64_t)c->fq_parses;
     else
         return fail(KGX_EINVAL, "unknown statistic " + n);
     return KGX_OK;

@@ -666,14 +666,19 @@ void *kgx_ctx_stream(kgx_ctx *ctx);
  * device path is the faster one measured (17 against 5.8 GB/s of text, BGZF
  * level 6); the default is 0 because it did not clear the
  * bar set for it at level 1 (16 x one-thread zlib).  KGX_GUNZIP_DEVICE=0|1 in
- * the environment sets the default of new contexts */
+ * the environment sets the default of new contexts.
+ * "fq_parse_device" 0 (default) / 1: kgx_f2p_process frames a part's FASTQ
+ * text with the host's strict parser / on the device (kgx_fq_parse); read when
+ * a file starts; the output does not change.  KGX_FQ_PARSE_DEVICE=0|1 in the
+ * environment sets the default of new contexts */
 int kgx_ctx_set_option(kgx_ctx *ctx, const char *name, int64_t value);
 /* counters of the context since its creation: "fused_batches" / "small_batches"
  * (small host batches that took the one-launch path / the one-wait path),
  * "stream_fallbacks" (streamed batches rerun exact after a region overflow or
  * a NUL in pinned input), "pinned_batches" (streamed batches read straight from
  * the caller's pinned residues), "nul_reruns", "lean_scores" (score stages
- * whose lane scorer was the lean kernel, option "score_lean") */
+ * whose lane scorer was the lean kernel, option "score_lean"), "fq_parses"
+ * (non-empty texts framed on the device, kgx_fq_parse / kgx_fq_parse_device) */
 int kgx_ctx_stat(kgx_ctx *ctx, const char *name, int64_t *value);
 /* launch on a caller-owned stream instead (hipStream_t; NULL = own stream) */
 int kgx_ctx_set_stream(kgx_ctx *ctx, void *stream);
@@ -1081,6 +1086,67 @@ typedef struct kgx_fq_text {
 int kgx_fq_proteins(kgx_ctx *ctx, const char *bases, const uint64_t *read_offsets, const char *ids,
                     const uint64_t *id_offsets, uint32_t n_reads, kgx_fq_text *out);
 
+/* ---- FASTQ text -> reads, on the device (kgx_fq_parse.hip)
+ * FastqParser::parse_char (fastq_parser.h:40-150) over text that begins at a
+ * record boundary: the id runs to the first blank, a definition line may
+ * follow it, the data line keeps its ASCII letters, the '+' line and the
+ * quality line are skipped whatever they hold, and a record ends at its
+ * quality line's newline.  An offending byte -- anything but '@' where a
+ * record starts, a data byte that is neither a letter nor the newline ('\r'
+ * and bytes >= 0x80 included), anything but '+' after the data line -- is
+ * dropped and leaves the parser where it is.
+ *
+ * Without KGX_FQ_STRICT the reads are the records ended by their quality
+ * newline, `consumed` is the end of the last of them (the caller feeds
+ * text[consumed, n) again in front of what comes next) and the error is the
+ * first offending byte before `consumed`, if any.  With KGX_FQ_STRICT the
+ * first offending byte e ends the parse, as under fastq_to_protein's callback
+ * (fastq_to_protein.cc:49-53): the reads are the records complete before e
+ * and then the record in progress with the id and bases it has in [.., e), an
+ * empty id included, and consumed = n.  With KGX_FQ_STRICT | KGX_FQ_FINISHED
+ * and no error the record in progress is a read if and only if it has an id
+ * (parse_complete) and consumed = n; with KGX_FQ_STRICT alone and no error
+ * the result is the one without it.  The error's id is the last read's.  A
+ * caller that parses a file in parts reports the line 1 + (the `newlines` of
+ * the earlier calls) + error_newlines.
+ *
+ * bases, read_offsets, ids and id_offsets are the context's own buffers, the
+ * ones kgx_fq_proteins fills (read_offsets[0] = id_offsets[0] = 0): they are
+ * valid until the context's next fq call, and kgx_fq_proteins_device runs
+ * kgx_fq_proteins' kernels over them without any copy.  bases and ids are
+ * followed by 16 allocated bytes each, as kgx_fq_proteins leaves them; nothing
+ * past bases[n_bases), ids[n_id_bytes) and the offsets' [n_reads + 1] is
+ * defined (a record in progress that is no read leaves its bytes there).
+ * d_text is device memory aligned to 16 bytes, of n bytes and no more; n is
+ * at most KGX_FQ_PARSE_MAX (byte positions and the sums over them are 32-bit
+ * on the device), KGX_ERANGE above it.  n = 0 gives zero reads and null
+ * arrays; KGX_EINVAL for a null argument, an unaligned d_text or an unknown
+ * flag.  Synchronous. */
+#define KGX_FQ_STRICT 1u   /* the first offending byte ends the parse (fastq_to_protein.cc:49-53) */
+#define KGX_FQ_FINISHED 2u /* the text ends the input (parse_complete) */
+#define KGX_FQ_PARSE_MAX 0xFFFFF000ull
+typedef struct kgx_fq_reads {
+    uint32_t n_reads, n_reads_no_id;
+    uint64_t n_bases, n_id_bytes;
+    const uint8_t *bases;         /* device */
+    const uint64_t *read_offsets; /* device: [n_reads + 1] */
+    const uint8_t *ids;           /* device */
+    const uint64_t *id_offsets;   /* device: [n_reads + 1] */
+    uint64_t consumed;            /* the caller feeds text[consumed, n) again, in front of what comes next */
+    uint64_t newlines;            /* '\n' in text[0, consumed) */
+    uint32_t error;               /* 0 none, 1 starts with '>', 2 missing '@', 3 bad data character, 4 missing '+' */
+    uint32_t error_byte;
+    uint64_t error_pos, error_newlines; /* the first offending byte; '\n' in text[0, error_pos] */
+    float upload_ms, parse_ms;          /* event times */
+} kgx_fq_reads;
+int kgx_fq_parse_device(kgx_ctx *ctx, const void *d_text, uint64_t n, uint32_t flags, kgx_fq_reads *out);
+/* host text: uploaded (by DMA straight from pinned memory, kgx_host_alloc;
+ * otherwise through the context's staging), then the above */
+int kgx_fq_parse(kgx_ctx *ctx, const char *text, uint64_t n, uint32_t flags, kgx_fq_reads *out);
+/* kgx_fq_proteins over the reads of this context's last kgx_fq_parse[_device]
+ * call; KGX_EINVAL for reads that are not those */
+int kgx_fq_proteins_device(kgx_ctx *ctx, const kgx_fq_reads *reads, kgx_fq_text *out);
+
 /* The tool as a streaming handle: FASTQ text in, FASTA text out.  Blocks may
  * cut a record anywhere; `finished` ends the file and resets the parser and
  * the error state for the next one.  Records are framed as the fq handler
@@ -1093,7 +1159,17 @@ int kgx_fq_proteins(kgx_ctx *ctx, const char *bases, const uint64_t *read_offset
  * inflated (kgx_gunzip on ctx) and their text processed.  part_bytes bounds
  * the FASTQ text taken per device pass (0: 32 MB, as the fq handler).  *text
  * is pinned host memory owned by the handle, valid until its next call.  One
- * context, no overlap of one part's download with the next part's kernels. */
+ * context, no overlap of one part's download with the next part's kernels.
+ *
+ * With the context's option "fq_parse_device" at 1 (read when a file starts) a
+ * part's text is uploaded and framed by kgx_fq_parse (KGX_FQ_STRICT, and
+ * KGX_FQ_FINISHED on the file's last part) and translated by
+ * kgx_fq_proteins_device; the host carries the part's unconsumed tail in
+ * front of the next bytes, and a part that holds no complete record while
+ * more input is to come is doubled instead of run again.  The text and every
+ * stat but the clocks are the host parser's; `parts` counts the device passes
+ * that held a read: more than the host path's where a part is part_bytes of
+ * carried tail plus new text, fewer where parts had to grow to hold a record. */
 typedef struct kgx_f2p kgx_f2p;
 typedef struct kgx_f2p_stats { /* since create or the last file's `finished` call, that call included */
     uint64_t reads;            /* records parsed */
@@ -1103,7 +1179,9 @@ typedef struct kgx_f2p_stats { /* since create or the last file's `finished` cal
     uint64_t parts;            /* device passes */
     uint32_t error_line;       /* line of the parse error (0: none) */
     uint32_t gzip;             /* 1: the file was gzip */
-    /* parse on the host (wall clock); the others stream time (HIP events) */
+    /* parse on the host (wall clock; "fq_parse_device" 1: the parse kernels'
+     * event time, and upload_ms includes the text's upload); the others stream
+     * time (HIP events) */
     double parse_ms, upload_ms, index_ms, sizes_ms, write_ms, download_ms;
 } kgx_f2p_stats;
 int kgx_f2p_create(kgx_ctx *ctx, uint64_t part_bytes, kgx_f2p **out);
