@@ -312,6 +312,7 @@ SIGNATURES = {
     "kgx_image_line_count": (_U64, [_P]),
     "kgx_image_line_home": (_U32, [_P]),
     "kgx_image_line_twins": (_U64, [_P]),
+    "kgx_image_line_pairs": (_U32, [_P]),
     "kgx_image_line_stats": (_INT, [_P, ctypes.POINTER(_U64)]),
     "kgx_image_set_filter": (_INT, [_P, _INT]),
     "kgx_image_download": (_INT, [_P, _P, _U64]),
@@ -617,6 +618,11 @@ class Image:
     def line_twins(self) -> int:
         """twin records in the line index (KGX_LINE_TWINS): the keys stored under two home lines"""
         return lib().kgx_image_line_twins(self.handle)
+
+    @property
+    def line_pairs(self) -> int:
+        """1 when the line index homes a 7-mer's two roles on the halves of a 128-byte block (KGX_LINE_PAIRS)"""
+        return lib().kgx_image_line_pairs(self.handle)
 
     LINE_STATS = ("stored", "past_home", "full_lines", "marked_lines", "mark_bits", "missing", "unjustified",
                   "reserved")

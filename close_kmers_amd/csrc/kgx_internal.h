@@ -163,8 +163,9 @@ hipError_t launch_plan_fused(const uint64_t *seq_off, uint32_t n_seq, uint64_t n
 
 /* ---- kgx_probe.hip: the probes ---- */
 /* Probes of PACKED16 records take the home word of kgx_line_home.h
- * (home_word: shift | home mode << 8 | overflow marks << 16 | twins << 17): a
- * key's home bucket is line_home(key, num_sigs >> shift, mode) << shift and
+ * (home_word: shift | home mode << 8 | overflow marks << 16 | twins << 17 |
+ * pairs << 18): a key's home bucket is home_bucket(key, num_sigs, magic, home),
+ * line_home(key, num_sigs >> shift, mode) << shift without pairs, and
  * num_sigs counts the table's buckets.  0: the reference's slot (key mod
  * num_sigs); shift 2: the line index of kgx_image_set_line_index (4-bucket
  * lines, homes at line starts), with the home mode the index was built with. */
@@ -180,7 +181,7 @@ struct ProbeTable {
     int layout = KGX_LAYOUT_PACKED16;   /* KGX_LAYOUT_* of the records */
     const uint64_t *filter = nullptr;   /* the presence filter's words, or none */
     uint32_t filter_log2_words = 0;
-    uint64_t magic() const { return mod_magic(num_sigs >> home_shift_of(home)); }
+    uint64_t magic() const { return mod_magic(home_magic_lines(num_sigs >> home_shift_of(home), home)); }
 };
 struct ProbeBatch {            /* a planned batch (launch_plan) */
     const uint8_t *bytes;      /* residues; launch_probe_dna: bases */

@@ -31,6 +31,23 @@
  * that home's walk placed, or the twin where it lies earlier on the chain.
  * The two copies differ in mark bits only.
  *
+ * Pairs (HOME_PAIRS_BIT, built only with twin records, over 3 lines or more).
+ * A 7-mer S owns a 128-byte block, the aligned lines 2k and 2k + 1 of the
+ * n_lines >> 1 blocks, k hashed from S as before: line 2k + 1 is the home of S
+ * as a key's first seven residues (role 1), line 2k its home as a key's last
+ * seven (role 0).  A key's two homes are those of its two 7-mers, each in its
+ * role; they differ in parity, so every key, homopolymers included, has two
+ * records.  The even window of a pair starts at line 2k and the odd one after
+ * it at 2k + 1: the neighbouring quads of one load instruction read the two
+ * halves of one block, a single 128-byte request, and a line collects the
+ * keys of one role only, at most 20 instead of 40.  Chains run on as before,
+ * line by line and wrapping at n_lines; with n_lines odd the last line is
+ * nobody's home and stays in the ring.  The minimizer home, where every other
+ * prober starts, is the home of the lower-hashing 7-mer in its role
+ * (pairs_minimizer_home).  The home functions under this layout take
+ * n_blocks = n_lines >> 1 and its magic, mod_magic(n_blocks): that is the
+ * magic the launchers carry for such an index (home_magic_lines).
+ *
  * The overflow marks (below) are set per key and per home from the finished
  * index: from each home of a stored key, every line before the first one that
  * holds the key carries the key's mark (lines_mark_kernel walks the index,
@@ -57,17 +74,23 @@ constexpr uint32_t LINE_HOME_MOD = 0, LINE_HOME_MINIMIZER = 1;
  * reference slots, 2 the 4-bucket lines of the index), bits 8-15 the
  * LINE_HOME_* mode of the image's index (0 where hs is 0), bit 16 set when
  * the index carries overflow marks (line_mark, below), bit 17 set when it
- * holds twin records (above). */
+ * holds twin records (above), bit 18 set when a 7-mer's two roles are homed
+ * on the halves of a 128-byte block (pairs, above). */
 constexpr uint32_t HOME_SHIFT_MASK = 0xFFu, HOME_MODE_SHIFT = 8, HOME_MODE_MASK = 0xFFu, HOME_MARKS_BIT = 1u << 16,
-                   HOME_TWINS_BIT = 1u << 17;
-KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode, bool marks = false, bool twins = false)
+                   HOME_TWINS_BIT = 1u << 17, HOME_PAIRS_BIT = 1u << 18;
+KGX_HD uint32_t home_word(uint32_t shift, uint32_t mode, bool marks = false, bool twins = false, bool pairs = false)
 {
-    return shift | mode << HOME_MODE_SHIFT | (marks ? HOME_MARKS_BIT : 0u) | (twins ? HOME_TWINS_BIT : 0u);
+    return shift | mode << HOME_MODE_SHIFT | (marks ? HOME_MARKS_BIT : 0u) | (twins ? HOME_TWINS_BIT : 0u) |
+           (pairs ? HOME_PAIRS_BIT : 0u);
 }
 KGX_HD uint32_t home_shift_of(uint32_t home) { return home & HOME_SHIFT_MASK; }
 KGX_HD uint32_t home_mode_of(uint32_t home) { return home >> HOME_MODE_SHIFT & HOME_MODE_MASK; }
 KGX_HD bool home_marks_of(uint32_t home) { return (home & HOME_MARKS_BIT) != 0; }
 KGX_HD bool home_twins_of(uint32_t home) { return (home & HOME_TWINS_BIT) != 0; }
+KGX_HD bool home_pairs_of(uint32_t home) { return (home & HOME_PAIRS_BIT) != 0; }
+/* what the homes of an index of n_lines are taken modulo, and whose magic the
+ * launchers carry: the lines, or under pairs the 128-byte blocks */
+KGX_HD uint64_t home_magic_lines(uint64_t n_lines, uint32_t home) { return home_pairs_of(home) ? n_lines >> 1 : n_lines; }
 
 /* x % n for x < 2^35, n >= 1, m = floor((2^64-1)/n): the quotient estimate
  * is exact or one short, so one conditional subtraction finishes it */
@@ -146,6 +169,54 @@ KGX_HD uint64_t pair_home(uint32_t a, uint32_t b, uint64_t g, uint64_t n_lines, 
     return seven_mer_home(g & 1u ? a : b, n_lines, magic);
 }
 
+/* Pairs: the home of 7-mer m in role r (1: a key's first seven residues, 0:
+ * its last seven), n_blocks = n_lines >> 1 >= 1, magic = mod_magic(n_blocks).
+ * The block is hashed as seven_mer_home hashes the line. */
+KGX_HD uint64_t pairs_seven_mer_home(uint32_t m, uint32_t hm, uint32_t r, uint64_t n_blocks, uint64_t magic)
+{
+    return 2 * seven_mer_home(m, hm, n_blocks, magic) + r;
+}
+KGX_HD uint64_t pairs_seven_mer_home(uint32_t m, uint32_t r, uint64_t n_blocks, uint64_t magic)
+{
+    return pairs_seven_mer_home(m, mix32(m), r, n_blocks, magic);
+}
+/* the two homes of the key whose 7-mers are a (first seven) and b (last seven) */
+KGX_HD uint64_t pairs_minimizer_home(uint32_t a, uint32_t b, uint64_t n_blocks, uint64_t magic)
+{
+    const uint32_t ha = mix32(a), hb = mix32(b);
+    return ha <= hb ? pairs_seven_mer_home(a, ha, 1u, n_blocks, magic) : pairs_seven_mer_home(b, hb, 0u, n_blocks, magic);
+}
+KGX_HD uint64_t pairs_twin_home(uint32_t a, uint32_t b, uint64_t n_blocks, uint64_t magic)
+{
+    const uint32_t ha = mix32(a), hb = mix32(b);
+    return ha <= hb ? pairs_seven_mer_home(b, hb, 0u, n_blocks, magic) : pairs_seven_mer_home(a, ha, 1u, n_blocks, magic);
+}
+/* where window g of a batch starts in the aligned line probe: at its last
+ * seven residues' home (line 2k) when g is even, at its first seven's (line
+ * 2k + 1) when g is odd; windows g (even) and g + 1 of one sequence share the
+ * 7-mer and so the block */
+KGX_HD uint64_t pairs_pair_home(uint32_t a, uint32_t b, uint64_t g, uint64_t n_blocks, uint64_t magic)
+{
+    return pairs_seven_mer_home(g & 1u ? a : b, (uint32_t)(g & 1u), n_blocks, magic);
+}
+
+/* The two homes of `key` under the home word of an index of n_lines (its mode,
+ * twins and pairs bits), magic = mod_magic(home_magic_lines(n_lines, home)):
+ * the builder's and the mark kernel's.  `other` equals `first` for a key
+ * with one home line. */
+KGX_HD void key_homes(uint64_t key, uint64_t n_lines, uint64_t magic, uint32_t home, uint64_t &first, uint64_t &other)
+{
+    const uint32_t a = (uint32_t)(key / 20u), b = (uint32_t)(key % 1280000000ull);
+    if (home_pairs_of(home)) {
+        first = pairs_minimizer_home(a, b, n_lines >> 1, magic);
+        other = pairs_twin_home(a, b, n_lines >> 1, magic);
+        return;
+    }
+    const uint32_t mode = home_mode_of(home);
+    first = mode == LINE_HOME_MOD ? mod_by(key, n_lines, magic) : minimizer_home(a, b, n_lines, magic);
+    other = home_twins_of(home) ? twin_home(a, b, n_lines, magic) : first;
+}
+
 /* the home line of `key` (<= 20^8) among n_lines, magic = mod_magic(n_lines) */
 KGX_HD uint64_t line_home(uint64_t key, uint64_t n_lines, uint64_t magic, uint32_t mode)
 {
@@ -176,10 +247,14 @@ KGX_HD bool line_index_aligned(uint64_t num_sigs, uint32_t home)
 }
 
 /* the home bucket of `key` in a probe table of num_sigs buckets; `home` as
- * above, magic = mod_magic(num_sigs >> hs) */
+ * above, magic = mod_magic(home_magic_lines(num_sigs >> hs, home)) */
 KGX_HD uint64_t home_bucket(uint64_t key, uint64_t num_sigs, uint64_t magic, uint32_t home)
 {
     const uint32_t hs = home_shift_of(home);
+    if (home_pairs_of(home)) {
+        const uint32_t a = (uint32_t)(key / 20u), b = (uint32_t)(key % 1280000000ull);
+        return pairs_minimizer_home(a, b, num_sigs >> hs >> 1, magic) << hs;
+    }
     return line_home(key, num_sigs >> hs, magic, home_mode_of(home)) << hs;
 }
 

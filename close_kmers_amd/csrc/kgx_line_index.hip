@@ -82,15 +82,18 @@ __global__ __launch_bounds__(256) void count_keys_kernel(const packed_bucket *__
  * buckets a line, by a 64-bit CAS on the record's first word.  A probe of the
  * line table from that home finds exactly the records the reference finds, so
  * results are unchanged while nearly every chain ends in its first 64-B line.
- * `twins` (the minimizer home only, kgx_line_home.h): the record is inserted
- * again by the same walk from its key's twin home, unless that is the same
- * line; *n_twins counts those second records. */
+ * `home` is the index's home word and line_magic the magic of what its homes
+ * are taken modulo (home_magic_lines).  Twins (the minimizer home only,
+ * kgx_line_home.h): the record is inserted again by the same walk from its
+ * key's twin home, unless that is the same line (under pairs it never is);
+ * *n_twins counts those second records. */
 __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *__restrict__ src, uint64_t num_sigs,
                                                           uint64_t src_magic, packed_bucket *lines, uint64_t n_lines,
-                                                          uint64_t line_magic, uint32_t home_mode, bool twins,
-                                                          uint32_t *overflow, unsigned long long *n_twins)
+                                                          uint64_t line_magic, uint32_t home_w, uint32_t *overflow,
+                                                          unsigned long long *n_twins)
 {
     const uint64_t NB = 4 * n_lines;
+    const bool twins = home_twins_of(home_w);
     uint64_t made = 0;
     for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < num_sigs;
          b += (uint64_t)gridDim.x * blockDim.x) {
@@ -108,12 +111,8 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
         }
         if (!first)
             continue;
-        const uint64_t home = line_home(key, n_lines, line_magic, home_mode);
-        uint64_t other = home;
-        if (twins) {
-            const uint32_t a7 = (uint32_t)(key / 20u), b7 = (uint32_t)(key % 1280000000ull);
-            other = twin_home(a7, b7, n_lines, line_magic);
-        }
+        uint64_t home, other;
+        key_homes(key, n_lines, line_magic, home_w, home, other);
         for (int copy = 0; copy < (other != home ? 2 : 1); copy++) {
             uint64_t x = (copy ? other : home) * 4;
             bool placed = false;
@@ -159,22 +158,19 @@ __global__ __launch_bounds__(256) void lines_build_kernel(const packed_bucket *_
  * halves both sums.  Without twins both are counted whole, as they were. */
 template <bool SCRATCH>
 __global__ __launch_bounds__(256) void lines_mark_kernel(packed_bucket *lines, uint64_t n_lines, uint64_t line_magic,
-                                                         uint32_t home_mode, bool twins, uint32_t *scratch,
+                                                         uint32_t home_w, uint32_t *scratch,
                                                          unsigned long long *stats)
 {
     const uint64_t NB = 4 * n_lines;
+    const bool twins = home_twins_of(home_w);
     uint64_t stored = 0, past = 0;
     for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < NB; b += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t key = lines[b].lo & PACK_KEY_MASK;
         if (key > MAX_ENCODED)
             continue;
         const uint64_t own = b / 4;
-        const uint64_t home = line_home(key, n_lines, line_magic, home_mode);
-        uint64_t other = home;
-        if (twins) {
-            const uint32_t a7 = (uint32_t)(key / 20u), b7 = (uint32_t)(key % 1280000000ull);
-            other = twin_home(a7, b7, n_lines, line_magic);
-        }
+        uint64_t home, other;
+        key_homes(key, n_lines, line_magic, home_w, home, other);
         const uint32_t n_homes = other != home ? 2 : 1;
         const uint32_t unit = twins && n_homes == 1 ? 2 : 1;
         stored += unit;
@@ -261,20 +257,22 @@ static hipError_t launch_count_keys(const packed_bucket *t, uint64_t n, unsigned
 }
 
 /* the line index of a PACKED16 table (lines_build_kernel): 4 * n_lines
- * buckets, homes by line_home(home_mode); *overflow |= 1 when some record
- * found no bucket; marks: then the overflow marks of kgx_line_home.h, by
- * lines_mark_kernel; twins (minimizer home with marks only): every key with
- * two home lines is stored under both, *n_twins += those second records */
+ * buckets, homes by the home word `home` (key_homes, kgx_line_home.h);
+ * *overflow |= 1 when some record found no bucket; with the word's marks bit:
+ * then the overflow marks, by lines_mark_kernel; with its twins bit (minimizer
+ * home with marks only): every key with two home lines is stored under both,
+ * *n_twins += those second records */
 static hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs, packed_bucket *lines,
-                                     uint64_t n_lines, uint32_t home_mode, bool marks, bool twins,
-                                     uint32_t *overflow, unsigned long long *n_twins, hipStream_t stream)
+                                     uint64_t n_lines, uint32_t home, uint32_t *overflow,
+                                     unsigned long long *n_twins, hipStream_t stream)
 {
+    const uint64_t line_magic = mod_magic(home_magic_lines(n_lines, home));
     hipLaunchKernelGGL(fill_empty_kernel, dim3(8192), dim3(256), 0, stream, lines, 4 * n_lines);
     hipLaunchKernelGGL(lines_build_kernel, dim3(8192), dim3(256), 0, stream, src, num_sigs, mod_magic(num_sigs), lines,
-                       n_lines, mod_magic(n_lines), home_mode, twins, overflow, n_twins);
-    if (marks)
-        hipLaunchKernelGGL(lines_mark_kernel<false>, dim3(8192), dim3(256), 0, stream, lines, n_lines,
-                           mod_magic(n_lines), home_mode, twins, nullptr, nullptr);
+                       n_lines, line_magic, home, overflow, n_twins);
+    if (home_marks_of(home))
+        hipLaunchKernelGGL(lines_mark_kernel<false>, dim3(8192), dim3(256), 0, stream, lines, n_lines, line_magic,
+                           home, nullptr, nullptr);
     return hipGetLastError();
 }
 
@@ -282,11 +280,11 @@ static hipError_t launch_lines_build(const packed_bucket *src, uint64_t num_sigs
  * home line (both twice over an index with twins, see lines_mark_kernel),
  * full lines, lines with a mark, mark bits set, missing and unjustified
  * marks; scratch: (n_lines + 1) / 2 zeroed words */
-static hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home_mode, bool twins,
-                                     uint32_t *scratch, unsigned long long *stats, hipStream_t stream)
+static hipError_t launch_lines_stats(const packed_bucket *lines, uint64_t n_lines, uint32_t home, uint32_t *scratch,
+                                     unsigned long long *stats, hipStream_t stream)
 {
     hipLaunchKernelGGL(lines_mark_kernel<true>, dim3(8192), dim3(256), 0, stream, const_cast<packed_bucket *>(lines),
-                       n_lines, mod_magic(n_lines), home_mode, twins, scratch, stats);
+                       n_lines, mod_magic(home_magic_lines(n_lines, home)), home, scratch, stats);
     hipLaunchKernelGGL(lines_stats_kernel, dim3(8192), dim3(256), 0, stream, lines, n_lines, scratch, stats);
     return hipGetLastError();
 }
@@ -338,6 +336,15 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     bool twins = minimizer && marks && keys_per_64_lines <= KGX_LINE_TWINS_MAX_LOAD;
     if (int rc = env_switch("KGX_LINE_TWINS", "none", "twins", twins))
         return rc;
+    /* pairs: a 7-mer's two roles homed on the halves of a 128-byte block
+     * (kgx_line_home.h), only where twins are built: KGX_LINE_PAIRS 1 turns
+     * them on, 0 off; unset they are on for an index of more than
+     * KGX_LINE_PAIRS_MIN_LINES lines (kgx.h); read at each call like the rest */
+    bool pairs = twins;
+    if (int rc = env_switch("KGX_LINE_PAIRS", "twins on one line", "pairs", pairs))
+        return rc;
+    const char *pairs_env = std::getenv("KGX_LINE_PAIRS");
+    const bool pairs_by_size = !pairs_env || !*pairs_env;
     /* the service's workgroups hold the probe table's address */
     const auto hold = svc_shutdown_hold(img);
     HIP_TRY(hipSetDevice(img->device));
@@ -362,6 +369,8 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
                                                         keys_per_64_lines));
     while (n_lines % 2 == 0 || n_lines % 5 == 0)
         n_lines++;
+    pairs = pairs && n_lines >= 3 && (!pairs_by_size || n_lines > KGX_LINE_PAIRS_MIN_LINES);
+    const uint32_t home = home_word(2u, home_mode, marks, twins, pairs);
     packed_bucket *lines = nullptr;
     if (e == hipSuccess && (4 * n_lines >= (1ull << 40) || hipMalloc(&lines, 4 * n_lines * sizeof(packed_bucket)) != hipSuccess)) {
         (void)hipGetLastError();
@@ -371,8 +380,7 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     uint32_t over = 0;
     unsigned long long n_twins = 0;
     if (e == hipSuccess)
-        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home_mode, marks, twins, d_over,
-                               d_count + 1, nullptr);
+        e = launch_lines_build(img->d_packed, img->num_sigs, lines, n_lines, home, d_over, d_count + 1, nullptr);
     if (e == hipSuccess)
         e = hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
@@ -389,6 +397,7 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
     img->lines.home = home_mode;
     img->lines.marks = marks;
     img->lines.twins = twins;
+    img->lines.pairs = pairs;
     img->lines.n_twins = n_twins;
     img->lines.load = keys_per_64_lines;
     return KGX_OK;
@@ -397,6 +406,7 @@ int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines)
 uint64_t kgx_image_line_count(const kgx_image *img) { return img ? img->lines.n_lines : 0; }
 uint32_t kgx_image_line_home(const kgx_image *img) { return img ? img->lines.home : 0; }
 uint64_t kgx_image_line_twins(const kgx_image *img) { return img ? img->lines.n_twins : 0; }
+uint32_t kgx_image_line_pairs(const kgx_image *img) { return img && img->lines.pairs ? 1u : 0u; }
 
 int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
 {
@@ -416,7 +426,7 @@ int kgx_image_line_stats(const kgx_image *img, uint64_t out[8])
     unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_scratch);
     hipError_t e = hipMemset(d_scratch, 0, words * 4 + 64);
     if (e == hipSuccess)
-        e = launch_lines_stats(li.records, li.n_lines, li.home, li.twins, d_scratch + 16, d_stats, nullptr);
+        e = launch_lines_stats(li.records, li.n_lines, li.home_word(), d_scratch + 16, d_stats, nullptr);
     unsigned long long h[8] = {};
     if (e == hipSuccess)
         e = hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost);

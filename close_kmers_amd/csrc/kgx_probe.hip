@@ -673,7 +673,9 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
          * (kgx_line_home.h), and a window starts at pair_home of its index in the
          * batch: g0, 64 j and the 16 windows of an instruction are all even, so
          * windows g (even) and g + 1 are neighbouring quads of one instruction
-         * and, in one sequence, ask for one line */
+         * and, in one sequence, ask for one line.  Under pairs (sp = 1) the
+         * shared 7-mer owns a 128-byte block and the two windows start on its
+         * halves, lines 2h and 2h + 1: eight lanes on one aligned block */
         static_assert(!MARKS || G == 4, "the index's lines are 4 records");
         static_assert(!TWINS || MARKS, "twin records come with marks only");
         if constexpr (MARKS) {
@@ -685,11 +687,12 @@ __global__ __launch_bounds__(256) void probe_line_kernel(
                 encode_tile<J>(residues, n_residues, seq_off, wbase, tile_seq[tile], W, g0, lane, code_tab, key, ok,
                                pos, sq, a7, b7);
             const uint32_t n_lines = (uint32_t)(num_sigs / G);
+            const uint32_t sp = home_pairs_of(home) ? 1u : 0u, n_homes = n_lines >> sp; /* magic is n_homes' */
             uint32_t home_line[J];
 #pragma unroll
             for (int j = 0; j < J; j++) {
-                if (TWINS)
-                    home_line[j] = ok[j] ? (uint32_t)pair_home(a7[j], b7[j], lane, n_lines, magic) : 0; /* g's parity is the lane's */
+                if (TWINS) /* g's parity is the lane's */
+                    home_line[j] = ok[j] ? (uint32_t)pair_home(a7[j], b7[j], lane, n_homes, magic) << sp | (lane & sp) : 0;
                 else
                     home_line[j] = ok[j] ? (uint32_t)line_home_7mers(a7[j], b7[j], n_lines, magic, home_mode_of(home)) : 0;
                 lds_hit[wave][64 * j + lane] = 0;

@@ -32,7 +32,7 @@ namespace kgx {
 /* sets the thread's kgx_last_error() text and returns code */
 int fail(int code, const std::string &msg);
 /* an on/off environment switch (KGX_LINE_HOME, KGX_LINE_MARKS, KGX_LINE_TWINS,
- * KGX_PROBE_DEFER): "0" clears `value`; "1", unset or empty leaves it at its
+ * KGX_LINE_PAIRS, KGX_PROBE_DEFER): "0" clears `value`; "1", unset or empty leaves it at its
  * default; anything else is KGX_EINVAL, with `zero` and `one` naming the two
  * settings */
 inline int env_switch(const char *name, const char *zero, const char *one, bool &value)
@@ -382,11 +382,12 @@ struct LineIndex {
     uint32_t home = LINE_HOME_MOD; /* the home mode it was built with */
     bool marks = false; /* it carries overflow marks (KGX_LINE_MARKS, kgx_line_home.h) */
     bool twins = false; /* it was built with twin records (KGX_LINE_TWINS, kgx_line_home.h) */
+    bool pairs = false; /* a 7-mer's two roles are homed on the halves of a 128-B block (KGX_LINE_PAIRS, kgx_line_home.h) */
     uint64_t n_twins = 0; /* how many: the keys with two home lines */
     uint32_t load = 0; /* keys per 64 lines it was built for */
     explicit operator bool() const { return records != nullptr; }
     /* what its probes take as ProbeTable.home */
-    uint32_t home_word() const { return kgx::home_word(2u, home, marks, twins); }
+    uint32_t home_word() const { return kgx::home_word(2u, home, marks, twins, pairs); }
 };
 
 }  // namespace kgx

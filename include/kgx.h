@@ -321,8 +321,27 @@ int kgx_image_set_layout(kgx_image *img, int layout);
  * doubled records would not fit at all.  The price at every load is paid by
  * the probers that start at the minimizer home: their chains cross the fuller
  * lines (the call service's p50 is a quarter longer at load 36, DESIGN.md
- * section 5); KGX_LINE_TWINS=0 is for images that serve those. */
+ * section 5); KGX_LINE_TWINS=0 is for images that serve those.
+ * Pairs.  Where twins are built and the index has at least 3 lines, a 7-mer
+ * can own an aligned 128-byte block, lines 2k and 2k + 1, instead of one line:
+ * the keys that end in it are homed on line 2k and the keys that begin with it
+ * on line 2k + 1.  Every stored key then has two records (its two homes differ
+ * in parity), a line collects at most 20 keys where it collected 40, and the
+ * two windows of a pair start on the two halves of one block, which the batch
+ * line probe reads by neighbouring quads of one instruction: one 128-byte
+ * request.  n_lines and the memory are unchanged; with n_lines odd the last
+ * line is nobody's home and chains wrap through it as before.  Every other
+ * prober starts at the home of the lower-hashing 7-mer in its role.  The
+ * environment variable KGX_LINE_PAIRS, read at each call like the three above:
+ * 1 builds pairs wherever this rule allows, 0 builds none, any other value is
+ * KGX_EINVAL with the index the image had kept; unset, pairs are built only
+ * for an index of more than KGX_LINE_PAIRS_MIN_LINES lines (256 MiB).  Small
+ * indexes keep the layout of the paragraphs above because the tests that
+ * restate its twin count and homes in Python are written for that layout and
+ * build small indexes; the layout pays only where the table is far larger than
+ * the caches anyway. */
 #define KGX_LINE_TWINS_MAX_LOAD 64u
+#define KGX_LINE_PAIRS_MIN_LINES (1ull << 22)
 int kgx_image_set_line_index(kgx_image *img, uint32_t keys_per_64_lines);
 /* lines of the image's line index (0: none) */
 uint64_t kgx_image_line_count(const kgx_image *img);
@@ -330,8 +349,10 @@ uint64_t kgx_image_line_count(const kgx_image *img);
  * no index, 1: minimizer) */
 uint32_t kgx_image_line_home(const kgx_image *img);
 /* twin records in the image's line index: the keys with two distinct home
- * lines (0: built without twins, or no index) */
+ * lines, under pairs every stored key (0: built without twins, or no index) */
 uint64_t kgx_image_line_twins(const kgx_image *img);
+/* 1 when the image's line index was built with pairs (KGX_LINE_PAIRS), else 0 */
+uint32_t kgx_image_line_pairs(const kgx_image *img);
 /* A device pass over the line index: out[0] stored keys (a key with a twin
  * record counts once), [1] records past their home line (with twins: pairs of
  * a key and one of its home lines where that line does not hold the key), [2] full lines, [3] lines with any overflow mark, [4] mark

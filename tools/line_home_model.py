@@ -16,6 +16,14 @@ index at the benchmark's ratios and counts those lines under
                home of its last seven residues and the odd window after it
                from the home of its first seven, the same 7-mer, so the two
                always share their line and one instruction serves both
+    pairs      twins with a 7-mer's two roles homed on the halves of a 128-byte
+               block (KGX_LINE_PAIRS): keys that end in the 7-mer on line 2k,
+               keys that begin with it on line 2k + 1 of the n_lines >> 1
+               blocks.  The even window starts at line 2k and the odd one after
+               it at 2k + 1, one aligned 128-byte request for the two; a line
+               collects one role's keys only.  Its rows count a block asked for
+               by a pair once (after the first lines the two chains are on
+               different blocks) and report the 64-byte lines fetched as well
 
 for stored keys, for absent keys, and for a query batch shaped like the
 benchmark's (half the sequences planted copies of source proteins with 10%
@@ -32,7 +40,7 @@ lines per absent key, and requests per window under two models of merging
 line a tile's windows touch is asked for once), and the fraction of lines that
 are full and were ever passed, the only ones a mark can sit on.
 
-For the twins rows it also counts the line probe's rounds (round_stats): the
+For the twins and pairs rows it also counts the line probe's rounds (round_stats): the
 share of 64-window slices whose longest chain has 2, 3, 4 or more lines, the
 chains a 128-window tile has open after every window's first line (mean, and
 how often more than the 16 that one load instruction serves), and the rounds
@@ -219,11 +227,21 @@ def round_stats(ql, slice_w=64, tile=128, quads=16):
     }
 
 
-def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
+def role_homes(keys, n_lines, alpha, pairs):
+    """the homes of a key's first and of its last seven residues and whether
+    the first is the minimizer; pairs: lines 2k + 1 and 2k of the 7-mers' blocks"""
+    if not pairs:
+        return seven_mer_homes(keys, n_lines, alpha)
+    a, b, amin = seven_mer_homes(keys, n_lines >> 1, alpha)
+    return 2 * a + 1, 2 * b, amin
+
+
+def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha, pairs=False):
     """the minimizer index with twin records, probed by the even/odd choice;
-    the columns of the other two homes"""
+    the columns of the other two homes.  pairs: the same over the halves of
+    128-byte blocks"""
     n = len(keys)
-    hA, hB, amin = seven_mer_homes(keys, n_lines, alpha)
+    hA, hB, amin = role_homes(keys, n_lines, alpha, pairs)
     two = hA != hB
     h1, h2 = np.where(amin, hA, hB), np.where(amin, hB, hA)
     at, occ = build(np.concatenate([h1, h2[two]]), n_lines)  # every record goes to its walk's first empty bucket
@@ -239,15 +257,16 @@ def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
     # queries: window g of the batch (sequences laid end to end) starts at
     # the home of its first 7-mer when g is odd, of its last when g is even
     odd = (np.arange(qk.size).reshape(qk.shape) & 1).astype(bool)
-    qA, qB, _ = seven_mer_homes(qk.ravel(), n_lines, alpha)
+    qA, qB, _ = role_homes(qk.ravel(), n_lines, alpha, pairs)
     qh = np.where(odd, qA.reshape(qk.shape), qB.reshape(qk.shape))
     pos = np.minimum(np.searchsorted(skeys, qk.ravel()), len(skeys) - 1)
     present = (skeys[pos] == qk.ravel()).reshape(qk.shape)
     idx = order[pos].reshape(qk.shape)
     ql_present = np.where(odd, dA[idx], dB[idx]) + 1
-    aA, aB, _ = seven_mer_homes(absent, n_lines, alpha)
+    aA, aB, _ = role_homes(absent, n_lines, alpha, pairs)
     ah = np.where(np.arange(len(absent)) & 1, aA, aB)
-    same = qh[:, 1:] == qh[:, :-1]
+    # neighbours that ask for one line (pairs: for the two halves of one block)
+    same = (qh[:, 1:] >> 1 == qh[:, :-1] >> 1) if pairs else (qh[:, 1:] == qh[:, :-1])
     pair = same & ~odd[:, :-1]  # the even window and the one after it: neighbouring quads of one instruction
     keys2, home2, walk2 = np.concatenate([keys, keys]), np.concatenate([hA, hB]), np.concatenate([dA, dB])
     variants = {}
@@ -259,20 +278,29 @@ def twins_model(keys, skeys, order, absent, qk, n_q, n_lines, alpha):
                           marked_chain(qk.ravel(), qh.ravel(), full, mk, n_lines, bits).reshape(qk.shape))
         else:
             mk, la, ql = np.zeros(n_lines, np.uint32), run[ah] + 1, np.where(present, ql_present, run[qh] + 1)
-        sv = np.where(pair, np.minimum(ql[:, 1:], ql[:, :-1]), 0)
+        # twins: the two chains of a pair walk the same lines; pairs: they share the first
+        # request, the block, and are on different blocks from then on
+        sv = np.where(pair, 1 if pairs else np.minimum(ql[:, 1:], ql[:, :-1]), 0)
         variants[str(bits)] = {
-            "query_lines_per_window": float(ql.mean()),
+            "query_lines_per_window": float(ql.mean()),  # the 64-B lines fetched
             "query_windows_past_first_line": float((ql > 1).mean()),
             "lines_per_absent_key": float(la.mean()),
             "query_lines_per_absent_window": float(ql[~present].mean()),
             "query_lines_per_present_window": float(ql[present].mean()),
             "query_requests_per_window": float((ql.sum() - sv.sum()) / ql.size),
+            "pairs_needing_more_than_one_request": float((np.maximum(ql[:, 1:], ql[:, :-1])[pair] > 1).mean()),
             "query_requests_per_window_tile_merge": float(tile_requests(qh, ql, n_lines)),
             "lines_marked": float((mk != 0).mean()),
             "mark_bits_per_marked_line": float(np.array([bin(int(v)).count("1") for v in mk[mk != 0][:100000]]).mean())
             if (mk != 0).any() else 0.0,
             "rounds": round_stats(ql),
         }
+        if pairs:
+            # the even window's second line is the half its neighbour has just fetched:
+            # a request still, but one the caches answer
+            reuse = (pair & (ql[:, :-1] > 1)).sum()
+            variants[str(bits)]["query_requests_per_window_neighbour_half_from_cache"] = float(
+                (ql.sum() - sv.sum() - reuse) / ql.size)
     q0 = variants["0"]
     return {
         "query_windows_absent": float((~present).mean()),
@@ -382,6 +410,7 @@ def model(alpha, seed, load=36):
         }
     del out["homes"]["twins"]
     out["homes"]["twins"] = twins_model(keys, skeys, np.argsort(keys), absent, qk, n_q, n_lines, alpha)
+    out["homes"]["pairs"] = twins_model(keys, skeys, np.argsort(keys), absent, qk, n_q, n_lines, alpha, pairs=True)
     return out
 
 

@@ -17,6 +17,13 @@
  * runs of one line are never longer than two quads.  A "window" is one quad
  * of one instruction, repeated or not.  One JSON object on stdout.
  *
+ *   halves   every even quad reads line 2k and the odd quad after it line
+ *            2k + 1 of one random aligned 128-B block (a 7-mer's block under
+ *            the pairs layout): 8 lanes on one block in one instruction.  It
+ *            is timed in alternation with form a at share 1/2, HALVES_REPEATS
+ *            times; a block there stands against a distinct line here, and
+ *            "halves_over_shared" is blocks/s over distinct lines/s.
+ *
  *   hipcc -O3 --offload-arch=gfx950 tools/line_share_probe.cpp -o tools/line_share_probe
  *   tools/line_share_probe [GiB of buffer, default 64] [device, default 0]
  */
@@ -96,6 +103,34 @@ __global__ __launch_bounds__(256) void share_kernel(const uint4 *__restrict__ ba
     sink[(uint64_t)blockIdx.x * blockDim.x + threadIdx.x] = acc;
 }
 
+/* quads 2i and 2i + 1 read the two halves of one random aligned 128-B block */
+__global__ __launch_bounds__(256) void halves_kernel(const uint4 *__restrict__ base, uint64_t n_blocks, uint64_t magic,
+                                                     uint64_t *__restrict__ sink)
+{
+    const uint64_t gw = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u, q = lane >> 2, c = lane & 3u;
+    uint64_t acc = 0;
+    for (uint32_t r = 0; r < ROUNDS; r++) {
+        uint64_t line[ILP];
+#pragma unroll
+        for (int k = 0; k < ILP; k++) {
+            const uint64_t at = (gw * ROUNDS + r) * ILP + k;
+            const uint64_t h = mix64(at * 16 + (q & ~1u));
+            line[k] = 2 * mod_by(h & ((1ull << 35) - 1), n_blocks, magic) + (q & 1u);
+        }
+        uint4 d[ILP];
+#pragma unroll
+        for (int k = 0; k < ILP; k++)
+            d[k] = base[line[k] * 4 + c];
+#pragma unroll
+        for (int k = 0; k < ILP; k++)
+            acc += ((uint64_t)d[k].y << 32 | d[k].x) ^ ((uint64_t)d[k].w << 32 | d[k].z);
+    }
+    sink[(uint64_t)blockIdx.x * blockDim.x + threadIdx.x] = acc;
+}
+
+constexpr int HALVES_REPEATS = 5;
+
 int main(int argc, char **argv)
 {
     const uint64_t gib = argc > 1 ? strtoull(argv[1], nullptr, 10) : 64;
@@ -156,6 +191,40 @@ int main(int argc, char **argv)
                    ms.back(), windows / (med * 1e-3), windows * (1.0 - s.share) / (med * 1e-3));
             first = false;
         }
+    }
+    /* the gate of the pairs layout: halves against the shared line, alternated */
+    const uint64_t n_blocks = n_lines >> 1, magic_blocks = ~0ull / n_blocks;
+    printf("], \"halves_blocks\": %llu, \"halves\": [", (unsigned long long)n_blocks);
+    for (int rep = 0; rep < HALVES_REPEATS; rep++) {
+        double med[2], lo[2], hi[2];
+        for (int form = 0; form < 2; form++) {
+            std::vector<float> ms;
+            for (int it = 0; it < 11; it++) {
+                CHECK(hipEventRecord(e0, nullptr));
+                if (form == 0)
+                    hipLaunchKernelGGL(share_kernel<false>, dim3(blocks), dim3(256), 0, nullptr, buf, n_lines, magic,
+                                       1024u, sink);
+                else
+                    hipLaunchKernelGGL(halves_kernel, dim3(blocks), dim3(256), 0, nullptr, buf, n_blocks,
+                                       magic_blocks, sink);
+                CHECK(hipGetLastError());
+                CHECK(hipEventRecord(e1, nullptr));
+                CHECK(hipEventSynchronize(e1));
+                float t = 0;
+                CHECK(hipEventElapsedTime(&t, e0, e1));
+                if (it >= 2)
+                    ms.push_back(t);
+            }
+            std::sort(ms.begin(), ms.end());
+            med[form] = ms[ms.size() / 2];
+            lo[form] = ms.front();
+            hi[form] = ms.back();
+        }
+        printf("%s{\"repeat\": %d, \"shared_median_ms\": %.4f, \"shared_min_ms\": %.4f, \"shared_max_ms\": %.4f, "
+               "\"shared_distinct_lines_per_s\": %.4g, \"halves_median_ms\": %.4f, \"halves_min_ms\": %.4f, "
+               "\"halves_max_ms\": %.4f, \"halves_blocks_per_s\": %.4g, \"halves_over_shared\": %.4f}",
+               rep ? ", " : "", rep, med[0], lo[0], hi[0], windows * 0.5 / (med[0] * 1e-3), med[1], lo[1], hi[1],
+               windows * 0.5 / (med[1] * 1e-3), med[0] / med[1]);
     }
     printf("]}\n");
     CHECK(hipFree(buf));
