@@ -230,18 +230,66 @@ __global__ void entries_insert_kernel(kgx_sig_kmer *t, uint64_t n, uint64_t magi
     }
 }
 
-__global__ void entries_payload_kernel(kgx_sig_kmer *t, uint64_t n, const int32_t *fi, const int32_t *otu,
-                                       const uint16_t *avg, const float *wt)
+/* the entries' own initial state: word 1 is entries_place_kernel's placement
+ * word, word 2 the owner as in synth_init_kernel */
+__global__ void entries_init_kernel(kgx_sig_kmer *t, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t *w = reinterpret_cast<uint64_t *>(t + i);
-        if (w[0] > MAX_ENCODED) {
+        w[0] = EMPTY_KEY;
+        w[1] = ~0ULL;
+        w[2] = ~0ULL;
+    }
+}
+
+/* The buckets the sequential builder gives the entries.  After
+ * entries_insert_kernel every stored bucket names, in word 2, the lowest entry
+ * index that holds its key; where that key sits was decided by the order of
+ * the threads.  KmerGuts::insert_kmer, taking the entries by index, puts entry
+ * e into the first bucket from its home that no earlier entry holds
+ * (kguts.cc:166-171,211).  This pass reaches that layout in any thread order:
+ * an entry claims a bucket's word 1 by atomicMin of its index; a bucket held
+ * by a lower index is passed, one held by a higher index is taken and that
+ * entry carried on from the next bucket (priority linear probing, Shun and
+ * Blelloch, "Phase-concurrent hash tables for determinism", SPAA 2014).
+ * Fewer than n / 2 entries: an empty bucket is met within n steps. */
+__global__ void entries_place_kernel(kgx_sig_kmer *t, uint64_t n, uint64_t magic, const uint64_t *keys)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t *w = reinterpret_cast<const uint64_t *>(t + i);
+        if (w[0] > MAX_ENCODED)
+            continue;
+        unsigned long long e = w[2];
+        uint64_t h = mod_by(keys[e], n, magic);
+        for (uint64_t probes = 0; probes < n; probes++) {
+            const unsigned long long old =
+                atomicMin(reinterpret_cast<unsigned long long *>(t + h) + 1, e);
+            if (old == ~0ULL)
+                break;
+            if (old > e)
+                e = old; /* the displaced entry goes on from the next bucket */
+            h = (h + 1 == n) ? 0 : h + 1;
+        }
+    }
+}
+
+__global__ void entries_payload_kernel(kgx_sig_kmer *t, uint64_t n, const uint64_t *keys, const int32_t *fi,
+                                       const int32_t *otu, const uint16_t *avg, const float *wt)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t *w = reinterpret_cast<uint64_t *>(t + i);
+        const uint64_t e = w[1];
+        if (e == ~0ULL) {
+            w[0] = EMPTY_KEY;
+            w[1] = 0;
             w[2] = 0;
             continue;
         }
-        const uint64_t e = w[2];
         kgx_sig_kmer *k = t + i;
+        k->which_kmer = keys[e];
         k->otu_index = otu[e];
         k->avg_from_end = avg[e];
         k->pad = 0;
@@ -255,11 +303,12 @@ hipError_t launch_entries_image(kgx_sig_kmer *table, uint64_t num_sigs, const ui
                                 uint64_t n_entries, unsigned long long *n_stored, hipStream_t stream)
 {
     const dim3 grid(8192), block(256);
-    hipLaunchKernelGGL(synth_init_kernel, grid, block, 0, stream, table, num_sigs);
+    hipLaunchKernelGGL(entries_init_kernel, grid, block, 0, stream, table, num_sigs);
     (void)hipMemsetAsync(n_stored, 0, sizeof(*n_stored), stream);
     hipLaunchKernelGGL(entries_insert_kernel, grid, block, 0, stream, table, num_sigs, mod_magic(num_sigs), keys,
                        n_entries, n_stored);
-    hipLaunchKernelGGL(entries_payload_kernel, grid, block, 0, stream, table, num_sigs, fi, otu, avg, wt);
+    hipLaunchKernelGGL(entries_place_kernel, grid, block, 0, stream, table, num_sigs, mod_magic(num_sigs), keys);
+    hipLaunchKernelGGL(entries_payload_kernel, grid, block, 0, stream, table, num_sigs, keys, fi, otu, avg, wt);
     return hipGetLastError();
 }
 

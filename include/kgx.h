@@ -240,8 +240,10 @@ int kgx_image_build_synthetic_distinct(uint64_t n_keys, uint64_t n_distinct, uin
  * KmerGuts::insert_kmer semantics (kguts.cc:166-228) -- keys above 20^8
  * are skipped, KGX_EFULL when the valid entries (duplicates included) reach
  * num_sigs / 2; of duplicated keys the lowest index is the one lookups find,
- * as with the sequential builder.  Bucket placement may differ from a
- * sequential build (parallel insertion); lookups are identical. */
+ * as with the sequential builder.  Distinct keys land in the buckets a
+ * sequential build in index order gives them (the table is, byte for byte,
+ * what save_kmer_hash_table writes); a duplicated key is stored once, where
+ * the sequential builder also stores its later copies. */
 int kgx_image_build(const uint64_t *keys, const int32_t *function_index, const int32_t *otu_index,
                     const uint16_t *avg_from_end, const float *function_wt, uint64_t n, uint64_t num_sigs,
                     int device, kgx_image **out, uint64_t *n_stored);

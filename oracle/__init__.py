@@ -146,16 +146,41 @@ def lib():
         L.oracle_fq_process.restype = vp
         L.oracle_fq_fragments.argtypes = [ctypes.c_char_p, u64]
         L.oracle_fq_fragments.restype = vp
+        L.oracle_fq_frames.argtypes = [ctypes.c_char_p, u64, ctypes.POINTER(u64)]
+        L.oracle_fq_frames.restype = vp
         _lib = L
     return _lib
 
 
+_ref_lib = None
+
+
 def ref_lib():
-    """The reference's own encoder / FASTA parser / translator / OTU sort
-    (oracle/_ref/libref.so), or None when it was not built."""
+    """The reference's own encoder / FASTA parser / translator / OTU sort /
+    KmerGuts over a KmerImage / FastqParser (oracle/_ref/libref.so), or None
+    when it was not built.  The reference prints to stdout and stderr as it
+    runs; nothing reads that."""
+    global _ref_lib
+    if _ref_lib is not None:
+        return _ref_lib
     if not os.path.exists(REF_LIB_PATH):
         return None
     L = ctypes.CDLL(REF_LIB_PATH)
+    vp, ul, cp = ctypes.c_void_p, ctypes.c_ulong, ctypes.c_char_p
+    L.ref_kg_open.argtypes = [cp]
+    L.ref_kg_open.restype = vp
+    L.ref_kg_close.argtypes = [vp]
+    L.ref_kg_process_aa.argtypes = [vp, vp, cp, ul, vp]
+    L.ref_kg_fetch.argtypes = [vp, vp, vp, vp]
+    L.ref_kg_find_best_call.argtypes = [vp, vp, ul, ctypes.POINTER(ctypes.c_int), cp, ul,
+                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
+    L.ref_kg_format_call.argtypes = [vp, vp, cp, ul]
+    L.ref_kg_format_hit.argtypes = [vp, vp, cp, ul]
+    L.ref_kg_format_otu_stats.argtypes = [vp, cp, ul, vp, ctypes.c_int, cp, ul]
+    L.ref_kg_build.argtypes = [ctypes.c_longlong, vp, vp, vp, vp, vp, ul, cp]
+    L.ref_fastq_parse.argtypes = [cp, ul, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ul)]
+    L.ref_fastq_parse.restype = vp
+    _ref_lib = L
     L.ref_encode.argtypes = [ctypes.c_char_p]
     L.ref_encode.restype = ctypes.c_ulonglong
     L.ref_decode.argtypes = [ctypes.c_ulonglong, ctypes.c_char_p]
@@ -169,6 +194,108 @@ def ref_lib():
     L.ref_translate11.restype = ctypes.c_void_p
     L.ref_free.argtypes = [ctypes.c_void_p]
     return L
+
+
+def _frames(text: bytes):
+    """Lines R<tab>id<tab>seq / E<tab>line<tab>id<tab>message -> (records, error)."""
+    records, error = [], None
+    for ln in text.split(b"\n")[:-1]:
+        f = ln.split(b"\t")
+        if f[0] == b"R":
+            records.append((f[1], f[2]))
+        else:
+            error = (b"\t".join(f[3:]).decode("latin-1"), int(f[1]), f[2])  # a message may quote a tab
+    return records, error
+
+
+def fq_frames(fastq: bytes):
+    """[(id, bases)] the oracle's fq request body frames out of a FASTQ text
+    (it goes on past errors and ends with parse_complete)."""
+    n = ctypes.c_uint64()
+    p = lib().oracle_fq_frames(fastq, len(fastq), ctypes.byref(n))
+    b = ctypes.string_at(p, n.value)
+    lib().oracle_free(p)
+    return _frames(b)[0]
+
+
+def ref_fastq_parse(fastq: bytes, stop_at_error: bool, parse_complete: bool):
+    """The reference's FastqParser over a text: ([(id, bases)], None or
+    (message, line, id) of the first error)."""
+    L = ref_lib()
+    n = ctypes.c_ulong()
+    p = L.ref_fastq_parse(fastq, len(fastq), int(stop_at_error), int(parse_complete), ctypes.byref(n))
+    b = ctypes.string_at(p, n.value)
+    L.ref_free(p)
+    return _frames(b)
+
+
+class RefKmerGuts:
+    """The reference's KmerGuts over a KmerImage of a data directory."""
+
+    def __init__(self, data_dir: str):
+        self.L = ref_lib()
+        self.h = self.L.ref_kg_open(data_dir.encode())
+
+    def process_aa(self, seq: bytes, params):
+        """(hits HIT_DTYPE, calls CALL_DTYPE, otus (n, 2) int32) of one
+        protein; params = (min_hits, max_gap, order_constraint,
+        min_weighted_hits), min_hits >= 2; seq holds no NUL byte."""
+        assert params[0] >= 2 and b"\0" not in seq
+        p4 = np.asarray(params, dtype=np.int32)
+        cnt = np.zeros(3, np.uint64)
+        self.L.ref_kg_process_aa(self.h, p4.ctypes.data, seq, len(seq), cnt.ctypes.data)
+        hits = np.zeros(int(cnt[0]), HIT_DTYPE)
+        calls = np.zeros(int(cnt[1]), CALL_DTYPE)
+        otus = np.zeros((int(cnt[2]), 2), np.int32)
+        self.L.ref_kg_fetch(self.h, hits.ctypes.data, calls.ctypes.data, otus.ctypes.data)
+        return hits, calls, otus
+
+    def find_best_call(self, calls: np.ndarray):
+        """(function_index, function, score, weighted_score, score_offset or None)."""
+        calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+        fi, off_set = ctypes.c_int(), ctypes.c_int()
+        buf = ctypes.create_string_buffer(1 << 16)
+        out3 = (ctypes.c_float * 3)()
+        self.L.ref_kg_find_best_call(self.h, calls.ctypes.data if len(calls) else None, len(calls),
+                                     ctypes.byref(fi), buf, len(buf), out3, ctypes.byref(off_set))
+        return (fi.value, buf.value.decode(), out3[0], out3[1], out3[2] if off_set.value else None)
+
+    def format_call(self, call) -> bytes:
+        c = np.ascontiguousarray(call, dtype=CALL_DTYPE).reshape(1)
+        buf = ctypes.create_string_buffer(1 << 12)
+        self.L.ref_kg_format_call(self.h, c.ctypes.data, buf, len(buf))
+        return buf.value
+
+    def format_hit(self, hit) -> bytes:
+        h = np.ascontiguousarray(hit, dtype=HIT_DTYPE).reshape(1)
+        buf = ctypes.create_string_buffer(1 << 12)
+        self.L.ref_kg_format_hit(self.h, h.ctypes.data, buf, len(buf))
+        return buf.value
+
+    def format_otu_stats(self, rid: bytes, size: int, otus) -> bytes:
+        o = np.ascontiguousarray(otus, dtype=np.int32).reshape(-1, 2)
+        buf = ctypes.create_string_buffer(1 << 12)
+        self.L.ref_kg_format_otu_stats(self.h, rid, size, o.ctypes.data if len(o) else None, len(o),
+                                       buf, len(buf))
+        return buf.value
+
+    def close(self):
+        if self.h:
+            self.L.ref_kg_close(self.h)
+            self.h = None
+
+
+def ref_build_image(num_buckets: int, keys, fI, oI, avg, wt, out_file: str) -> None:
+    """The reference's loading KmerGuts: insert_kmer in the given order, then
+    save_kmer_hash_table to out_file.  len(keys) + 1 < num_buckets // 2."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert len(keys) + 1 < num_buckets // 2
+    fI = np.ascontiguousarray(fI, dtype=np.int32)
+    oI = np.ascontiguousarray(oI, dtype=np.int32)
+    avg = np.ascontiguousarray(avg, dtype=np.uint16)
+    wt = np.ascontiguousarray(wt, dtype=np.float32)
+    ref_lib().ref_kg_build(num_buckets, keys.ctypes.data, fI.ctypes.data, oI.ctypes.data, avg.ctypes.data,
+                           wt.ctypes.data, len(keys), out_file.encode())
 
 
 @dataclass

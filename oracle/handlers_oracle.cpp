@@ -789,6 +789,20 @@ char *oracle_fq_process(void *p, const char *fastq, uint64_t n)
     return b;
 }
 
+/* the (id, bases) records the fq request body sees for a FASTQ text, as
+ * "R\t<id>\t<bases>\n" lines in stream order (an id holds no tab) */
+char *oracle_fq_frames(const char *fastq, uint64_t n, uint64_t *out_len)
+{
+    std::string s;
+    parse_fastq(std::string(fastq, n), [&](const std::string &id, const std::string &seq) {
+        s += "R\t" + id + "\t" + seq + "\n";
+    });
+    char *b = static_cast<char *>(std::malloc(s.size() + 1));
+    std::memcpy(b, s.c_str(), s.size() + 1);
+    *out_len = s.size();
+    return b;
+}
+
 /* /lookup session: table (borrowed), functions, family DB files, and an
  * optional /add FASTA filling kmer_to_id_ first (add_request.cc:164-170) */
 void *oracle_lookup_new(const void *table, uint64_t num_sigs, const char *const *functions, uint64_t n_functions,

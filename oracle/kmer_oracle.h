@@ -7,16 +7,13 @@
  * cpu_baseline leg may link, load or run anything built from oracle/.  The
  * product library never includes this header.
  *
- * Parity status (see DESIGN.md "Oracle"): the reference's own kguts.cc and
- * kmer_image.cc include boost headers that this image lacks, so they are
- * unbuildable here.  This restatement is pinned by:
- *   - the reference's KmerEncoder (kmer_encoder.cc), KmerOtuStats (kguts.h),
- *     FastaParser (fasta_parser.cc) and TranslationTable (trans_table.cc),
- *     compiled from /root/reference into oracle/_ref/ (see oracle/Makefile);
- *   - the known-answer example in SCORING.txt:15-20,28-49,84-97.
- * The probe loop and the gather_hits/process_set_of_hits state machine are
- * restated line by line from kguts.cc (cited per function) and are otherwise
- * "parity partially pinned" (SCORING.txt's HIT->CALL example only).
+ * Parity status (see DESIGN.md "Oracle"): this restatement is pinned, bit for
+ * bit, by runs of the reference's own code compiled from its sources into
+ * oracle/_ref/ (see oracle/Makefile): KmerEncoder, KmerOtuStats, FastaParser,
+ * TranslationTable, KmerGuts over a KmerImage (the probe loop, gather_hits,
+ * process_set_of_hits, find_best_call, format_*, insert_kmer and
+ * save_kmer_hash_table) and FastqParser; and by the known-answer example in
+ * SCORING.txt:15-20,28-49,84-97.  tests/test_reference_pin.py.
  */
 #ifndef KMER_ORACLE_H
 #define KMER_ORACLE_H
