@@ -1248,7 +1248,11 @@ const char *kgx_f2p_error(const kgx_f2p *h);
  * ISIZE (or than the room given), 14 output shorter than ISIZE, 15 CRC-32
  * mismatch; framing: 32 not gzip, 33 method not deflate, 34 reserved flag
  * bits, 35 member cut short, 36 BSIZE does not cover header and trailer,
- * 37 blocked member with ISIZE above 65,536, 38 header CRC. */
+ * 37 blocked member with ISIZE above 65,536, 38 header CRC.
+ * Within the last 15 bits of a member's deflate data, 12 can stand for 10:
+ * bits that are no code of an incomplete set, with fewer bits left than the
+ * longest code has, are reported as the end of the input.  Host and device
+ * report the same, and the member is refused either way. */
 typedef struct kgx_inflate_stats {
     uint32_t stored_blocks, fixed_blocks, dynamic_blocks; /* blocks by type */
     uint32_t max_code_len; /* longest code length of a dynamic block's codes */

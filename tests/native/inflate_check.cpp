@@ -19,6 +19,9 @@
  *   trunc IN          every proper prefix of one blocked member's deflate
  *                     data, decoded into room for ISIZE
  *     -> trunc <prefixes> <failed> <ok>
+ *   pack IN OUT       many raw streams, each with its room, from one file
+ *                     (run_pack), the results and outputs into OUT
+ *     -> pack <streams> <ok> <failed>
  */
 #include <cstdio>
 #include <cstdlib>
@@ -209,6 +212,51 @@ static int run_trunc(const std::string &data)
     return 0;
 }
 
+/* many raw streams from one file, each a record {u32 length, u32 room, bytes};
+ * OUT gets a record per stream: {u32 reason, u32 out_len, u64 bit_pos,
+ * u32 stats[8], the out_len bytes}.  Input and room are heap blocks of exactly
+ * their size, as for the single cases. */
+static int run_pack(const std::string &data, const std::string &out_path)
+{
+    std::ofstream o(out_path, std::ios::binary);
+    auto tables = std::make_unique<InflateTables>();
+    unsigned n = 0, ok = 0, failed = 0;
+    size_t at = 0;
+    while (at + 8 <= data.size()) {
+        uint32_t len, cap;
+        std::memcpy(&len, data.data() + at, 4);
+        std::memcpy(&cap, data.data() + at + 4, 4);
+        at += 8;
+        if (len > data.size() - at)
+            break;
+        Heap in(len), out(cap);
+        std::memcpy(in.p, data.data() + at, len);
+        at += len;
+        InflateStats st;
+        HostIO io;
+        const InflateResult r = inflate_raw(in.p, in.p + len, out.p, out.p + cap, tables.get(), &st, io);
+        if (r.out_len > cap) { /* never; and then not read back either */
+            std::printf("pack stream %u: out_len %llu above its room %u\n", n, (unsigned long long)r.out_len, cap);
+            return 0;
+        }
+        const uint32_t head[2] = {r.reason, (uint32_t)r.out_len};
+        const uint64_t bit = r.bit_pos;
+        const uint32_t s[8] = {st.stored_blocks, st.fixed_blocks, st.dynamic_blocks, st.max_code_len,
+                               st.max_distance,  st.max_length,   st.overlap,        st.matches};
+        o.write(reinterpret_cast<const char *>(head), sizeof head);
+        o.write(reinterpret_cast<const char *>(&bit), sizeof bit);
+        o.write(reinterpret_cast<const char *>(s), sizeof s);
+        o.write(reinterpret_cast<const char *>(out.p), (std::streamsize)r.out_len);
+        n++;
+        if (r.reason)
+            failed++;
+        else
+            ok++;
+    }
+    std::printf("pack %u %u %u\n", n, ok, failed);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc != 2) {
@@ -237,6 +285,8 @@ int main(int argc, char **argv)
             run_crc(data);
         else if (mode == "trunc")
             run_trunc(data);
+        else if (mode == "pack")
+            run_pack(data, out_path);
         else
             std::printf("%s unknown-mode\n", mode.c_str());
     }

@@ -1,12 +1,17 @@
 """kgx_inflate_host, kgx_gunzip_scan and the host side of kgx_gunzip (no
 context: blocked members on host threads, plain members on the caller's)
-through abi.py.  No GPU."""
+through abi.py: the decode and error cases of bgzf_util (every decoder reason
+by a hand-made member, the legal incomplete distance sets, the geometry,
+stored-geometry and size members, these also one by one with their
+statistics), the first 512 streams of the mutated corpus against zlib's
+verdicts, raw and wrapped as blocked members, and single members with every
+optional header field against zlib.decompressobj(31).  No GPU."""
 import zlib
 
 import pytest
 
 import bgzf_util as bz
-from test_inflate_native import check_stats
+from test_inflate_native import check_corpus_stream, check_stats
 
 
 @pytest.fixture(scope="module")
@@ -116,6 +121,106 @@ def test_gunzip_error_cases(abi):
     with pytest.raises(abi.KgxError) as e:
         abi.gunzip(None, bad, cap=len(text))
     assert e.value.code == abi.KGX_EFORMAT and f"reason {bz.CRC}" in str(e.value)
+
+
+def test_member_sets_member_by_member(abi):
+    """the geometry, stored-geometry and size members one by one through
+    kgx_inflate_host in a room of exactly the text: the text, the input used
+    and the statistics of the member's one match"""
+    for p, dist, length, m, text in bz.geometry_members():
+        rc, out, used, st, reason, bit = abi.inflate_host(m[18:-8], len(text))
+        assert (rc, reason, out, used) == (0, 0, text, len(m) - 26), (p, dist, length)
+        assert (st["matches"], st["max_distance"], st["max_length"], st["overlap"]) == \
+            (1, dist, length, int(dist < length)), (p, dist, length, st)
+    for p, s, dist, length, m, text in bz.stored_members():
+        rc, out, used, st, reason, bit = abi.inflate_host(m[18:-8], len(text))
+        assert (rc, reason, out, used) == (0, 0, text, len(m) - 26), (p, s)
+        assert (st["matches"], st["max_distance"], st["max_length"], st["stored_blocks"], st["fixed_blocks"]) == \
+            (1, dist, length, 1, 2), (p, s, st)
+    for n, m, text in bz.size_members():
+        rc, out, used, st, reason, bit = abi.inflate_host(m[18:-8], n)
+        assert (rc, reason, out, used) == (0, 0, text, len(m) - 26), n
+        # one byte less room: refused, and what was produced is the text's beginning
+        rc, out, used, st, reason, bit = abi.inflate_host(m[18:-8], n - 1)
+        assert (rc, reason) == (abi.KGX_EFORMAT, bz.OUTPUT_FULL) and out == text[:len(out)], n
+
+
+def test_error_case_prefixes(abi):
+    """what a failing stream produced before it failed is there and counted"""
+    for name, prefix in bz.error_case_prefixes().items():
+        m = bz.error_cases()[name][0]
+        rc, out, used, st, reason, bit = abi.inflate_host(m[18:-8], int.from_bytes(m[-4:], "little"))
+        assert rc == abi.KGX_EFORMAT and out == prefix, (name, out)
+
+
+CORPUS_SLICE = 512  # of bz.corpus(): the streams the GPU test gives to the kernel
+
+
+def test_corpus_slice_through_the_library(abi):
+    """the first 512 streams of the corpus through kgx_inflate_host, with the
+    rooms and the requirements of test_inflate_native.test_mutated_corpus_against_zlib"""
+    for i, entry in enumerate(bz.corpus()[:CORPUS_SLICE]):
+        raw, ok, text, _ = entry
+        rc, out, used, st, reason, bit = abi.inflate_host(raw, bz.corpus_room(ok, text))
+        assert (rc == 0) == (reason == 0) and used == (bit + 7) // 8
+        check_corpus_stream(i, entry, dict(reason=reason, out_len=len(out), bit=bit), out)
+        if reason:
+            assert f"reason {reason})" in abi.last_error() and f"at bit {bit}" in abi.last_error(), i
+
+
+def test_corpus_slice_as_blocked_members(abi):
+    """the same streams wrapped as blocked members through kgx_gunzip without a
+    context: those zlib accepts as one body, whose text is zlib's; every one
+    it rejects in the middle of accepted ones, where the error names its index
+    and the reason kgx_inflate_host gave for the stream"""
+    part = bz.corpus()[:CORPUS_SLICE]
+    good = [(bz.bgzf_member(raw, text), text) for raw, ok, text, _ in part if ok]
+    assert len(good) >= CORPUS_SLICE // 4
+    body, text = b"".join(m for m, _ in good), b"".join(t for _, t in good)
+    out, consumed, st = abi.gunzip(None, body)
+    assert out == text and consumed == len(body) and st["host_blocked_members"] == len(good)
+    front, back = b"".join(m for m, _ in good[:5]), b"".join(m for m, _ in good[5:8])
+    rejected = 0
+    for raw, ok, text, _ in part:
+        if ok:
+            continue
+        room = bz.corpus_room(ok, text)
+        reason = abi.inflate_host(raw, room)[4]
+        with pytest.raises(abi.KgxError) as e:
+            abi.gunzip(None, front + bz.bgzf_member(raw, b"", crc=0x12345678, isize=room) + back)
+        assert e.value.code == abi.KGX_EFORMAT and "member 5:" in str(e.value) and \
+            f"(reason {reason})" in str(e.value), (rejected, str(e.value))
+        assert "member 5:" in abi.last_error() and f"(reason {reason})" in abi.last_error()
+        rejected += 1
+    assert rejected >= CORPUS_SLICE // 4
+
+
+def test_header_variants_against_zlib(abi):
+    """single members with every optional header field (RFC 1952 2.3) against
+    zlib.decompressobj(31): the same verdict and the same text; the framing
+    walk's `blocked` says which it took as blocked members (a BC subfield of
+    length 2 anywhere in the extra field)"""
+    g = bz.golden()[:3000]
+    for name, (body, blocked) in bz.gzip_header_variants().items():
+        want = bz.zlib_gunzip(body)
+        try:
+            out, consumed, st = abi.gunzip(None, body, cap=len(g))
+        except abi.KgxError as e:
+            assert e.code == abi.KGX_EFORMAT, name
+            out = None
+            assert "member 0:" in str(e), (name, str(e))
+            assert ("reason 38" if "fhcrc" in name else "reason 35") in str(e), (name, str(e))
+        assert out == want, name
+        if want is not None:
+            assert want == g and consumed == len(body), name
+            assert (st["host_blocked_members"], st["plain_members"]) == ((1, 0) if blocked else (0, 1)), name
+            assert abi.gunzip_scan(body) == {"members": 1, "blocked": int(blocked),
+                                            "out_bytes": len(g) if blocked else 0,
+                                            "consumed": len(body) if blocked else 0}, name
+        else:
+            assert not blocked
+            with pytest.raises(abi.KgxError):
+                abi.gunzip_scan(body)
 
 
 @pytest.mark.parametrize("step", (1, 17, 4096))
