@@ -227,6 +227,27 @@ class FqReads(ctypes.Structure):
         return t + chr(self.error_byte) + "'" if self.error == 3 else t
 
 
+FA_STRICT, FA_FINISHED = 1, 2  # KGX_FA_STRICT, KGX_FA_FINISHED
+FA_PARSE_MAX = 0xFFFFF000      # KGX_FA_PARSE_MAX
+# kgx_fa_seqs.error -> the reference's wording (fasta_parser.h:54-132); 2 and 3 are followed by the byte and "'"
+FA_ERROR_TEXT = ("", "Missing >", "Bad data character '", "Bad id or data character '")
+
+
+class FaSeqs(ctypes.Structure):
+    """kgx_fa_seqs: the sequences of a FASTA text, framed on the device."""
+    _fields_ = [("n_seqs", ctypes.c_uint32), ("n_seqs_no_id", ctypes.c_uint32), ("n_residues", ctypes.c_uint64),
+                ("n_id_bytes", ctypes.c_uint64), ("residues", ctypes.c_void_p), ("seq_offsets", ctypes.c_void_p),
+                ("ids", ctypes.c_void_p), ("id_offsets", ctypes.c_void_p), ("consumed", ctypes.c_uint64),
+                ("newlines", ctypes.c_uint64), ("error", ctypes.c_uint32), ("error_byte", ctypes.c_uint32),
+                ("error_pos", ctypes.c_uint64), ("error_newlines", ctypes.c_uint64),
+                ("upload_ms", ctypes.c_float), ("parse_ms", ctypes.c_float)]
+
+    def error_text(self) -> str:
+        """The reference's words for the error ("" if none)."""
+        t = FA_ERROR_TEXT[self.error]
+        return t + chr(self.error_byte) + "'" if self.error in (2, 3) else t
+
+
 class F2pStats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint64) for k in ("reads", "reads_no_id", "fragments", "text_bytes", "parts")] + \
         [("error_line", ctypes.c_uint32), ("gzip", ctypes.c_uint32)] + \
@@ -349,6 +370,8 @@ SIGNATURES = {
     "kgx_fq_parse": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
     "kgx_fq_parse_device": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
     "kgx_fq_proteins_device": (_INT, [_P, ctypes.POINTER(FqReads), ctypes.POINTER(FqText)]),
+    "kgx_fa_parse": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FaSeqs)]),
+    "kgx_fa_parse_device": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FaSeqs)]),
     "kgx_f2p_create": (_INT, [_P, _U64, _PP]),
     "kgx_f2p_destroy": (_INT, [_P]),
     "kgx_f2p_process": (_INT, [_P, _CS, _U64, _INT, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_U64)]),
@@ -962,6 +985,42 @@ class Context:
             params = parse_params(params)
         check(lib().kgx_fq_run_device(self.handle, ctypes.byref(params), ctypes.byref(f), want, None),
               "kgx_fq_run_device")
+        r = Result()
+        check(lib().kgx_device_batch_collect(self.handle, want, ctypes.byref(r)), "collect")
+        return BatchResult(r, want)
+
+    def fa_parse(self, text: bytes, flags: int = 0) -> FaSeqs:
+        """kgx_fa_parse: host FASTA text framed on the device, the sequences left there."""
+        text = bytes(text)
+        r = FaSeqs()
+        check(lib().kgx_fa_parse(self.handle, _bytes_ptr(text), len(text), flags, ctypes.byref(r)), "kgx_fa_parse")
+        return r
+
+    def fa_parse_device(self, d_text: int, n: int, flags: int = 0) -> FaSeqs:
+        """kgx_fa_parse_device: n bytes of FASTA text in device memory (16-byte aligned)."""
+        r = FaSeqs()
+        check(lib().kgx_fa_parse_device(self.handle, d_text, n, flags, ctypes.byref(r)), "kgx_fa_parse_device")
+        return r
+
+    def fa_seqs_to_host(self, r: FaSeqs, arrays=("residues", "seq_offsets", "ids", "id_offsets")) -> dict:
+        """Host copies of a kgx_fa_seqs' arrays (tests / tools)."""
+        n_off = r.n_seqs + 1 if r.seq_offsets else 0
+        out = {"residues": np.zeros(r.n_residues, np.uint8), "seq_offsets": np.zeros(n_off, np.uint64),
+               "ids": np.zeros(r.n_id_bytes, np.uint8), "id_offsets": np.zeros(n_off, np.uint64)}
+        out = {k: out[k] for k in arrays}
+        for k, a in out.items():
+            if a.nbytes and getattr(r, k):
+                check(lib().kgx_memcpy_d2h(a.ctypes.data, getattr(r, k), a.nbytes), "d2h")
+        return out
+
+    def run_parsed(self, seqs: FaSeqs, params: Params | dict | None = None,
+                   want: int = WANT_HITS | WANT_CALLS) -> BatchResult:
+        """The lookup over a fa_parse's sequences where the parse left them,
+        results collected to the host."""
+        if params is None or isinstance(params, dict):
+            params = parse_params(params)
+        check(lib().kgx_run_device(self.handle, ctypes.byref(params), seqs.residues, seqs.seq_offsets, seqs.n_seqs,
+                                   seqs.n_residues, want, None), "kgx_run_device")
         r = Result()
         check(lib().kgx_device_batch_collect(self.handle, want, ctypes.byref(r)), "collect")
         return BatchResult(r, want)

@@ -490,6 +490,9 @@ struct kgx_ctx {
     kgx::DevBuf fp_text, fp_map, fp_state, fp_lane, fp_cnt, fp_pre, fp_sum;
     kgx::PinnedVec<uint64_t> h_fp_sum;
     std::vector<hipEvent_t> fp_events; /* timing: upload start, parse start, parse end */
+    /* kgx_fa_parse (kgx_fa_parse.hip): the last FASTA text's residues, sequence
+     * offsets, ids and id offsets; its scratch is the fp_* above */
+    kgx::DevBuf fa_res, fa_soff, fa_ids, fa_idoff;
     /* kgx_gunzip / kgx_gunzip_device (kgx_gunzip.cpp) */
     kgx::DevBuf gz_in, gz_out, gz_members, gz_status, gz_stats;
     kgx::PinnedVec<kgx_gz_member> h_gz_members;

@@ -9,11 +9,14 @@ grouping and the order are made on the device (abi.Unique, csrc/kgx_uniq.hip,
 DESIGN.md §8.10); the host reads the FASTA and writes the text.
 
     python -m close_kmers_amd.unique_prots DATA_DIR FASTA [FASTA ...] [--device N] [--output FILE] \\
-        [--piece-residues N]
+        [--piece-residues N] [--parse-device]
 
 Several FASTA files are read as one input, in order.  Ids are the definition
 lines' first words; a record with an empty id is kept, as the reference's
-parser calls back for it.
+parser calls back for it.  With --parse-device (off by default) the files are
+framed by the device parser (fasta_device.read_records), so
+the records are the reference's FastaParser's where the host reader differs:
+"> x" has an empty id, a byte the parser reports is dropped.
 """
 from __future__ import annotations
 
@@ -53,10 +56,16 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--output", help="file for the text (default: stdout)")
     ap.add_argument("--piece-residues", type=int, default=0, help="residues per device piece (0: the library's default)")
+    ap.add_argument("--parse-device", action="store_true",
+                    help="frame the FASTA files on the device, as the reference's parser frames them (default: off)")
     a = ap.parse_args(argv)
     from . import abi
-    records = [recall.read_fasta_all(p) for p in a.fasta]
+    if not a.parse_device:
+        records = [recall.read_fasta_all(p) for p in a.fasta]
     with abi.Image.open(a.data, a.device) as img, abi.Context(img) as ctx:
+        if a.parse_device:
+            from . import fasta_device
+            records = [fasta_device.read_records(ctx, p) for p in a.fasta]
         text, _ = unique(ctx, records, a.piece_residues)
     if a.output:
         with open(a.output, "wb") as f:

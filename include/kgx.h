@@ -1170,6 +1170,78 @@ int kgx_fq_parse(kgx_ctx *ctx, const char *text, uint64_t n, uint32_t flags, kgx
  * call; KGX_EINVAL for reads that are not those */
 int kgx_fq_proteins_device(kgx_ctx *ctx, const kgx_fq_reads *reads, kgx_fq_text *out);
 
+/* ---- FASTA text -> sequences, on the device (kgx_fa_parse.hip, DESIGN.md
+ * §8.13).  FastaParser::parse_char (fasta_parser.h:38-144) over text that
+ * begins at a record boundary: five states (start, id, defline, data,
+ * id-or-data: the start of a line after the record's first data line).  '\r'
+ * is skipped in every state and is no newline.  '>' opens a record from start
+ * and from id-or-data; the id runs to the first blank (space or tab), a
+ * definition line may follow it (not produced); in data a letter or '*' is a
+ * residue, in id-or-data a letter is.  A record ends at the '>' that opens the
+ * next one.  An offending byte leaves the parser where it is and is dropped:
+ * 1 "Missing >": in start anything but '>', '\n' included; 2 "Bad data
+ * character 'X'": in data anything but '\n', a letter or '*', so a '>' on the
+ * line after a header is one and that second header's letters are residues of
+ * the first record; 3 "Bad id or data character 'X'": in id-or-data anything
+ * but '>', '\n' or a letter, so '*' first on a later line is one.  Bytes >=
+ * 0x80 are neither letters nor blanks.
+ *
+ * Without flags the sequences are the records ended by a following '>',
+ * `consumed` is the position of the last such '>' (0 when there is none: the
+ * caller feeds text[consumed, n) again in front of what comes next, and a
+ * re-fed tail starts with its '>', which puts the parser where it was),
+ * `newlines` counts '\n' in text[0, consumed) and the error is the first
+ * offending byte before `consumed`, if any; later ones are dropped, as the
+ * reference's parser prints them and goes on.  With KGX_FA_FINISHED the
+ * record in progress at the end of the text is a sequence too, whatever it
+ * holds (parse_complete): n_seqs is the ends + 1, consumed = n, newlines
+ * counts the whole text; an empty text is one record with an empty id and no
+ * residues.  With KGX_FA_STRICT the first offending byte e ends the parse, as
+ * under validate_fasta's callback (validate_fasta.cc:35-40): the sequences are
+ * those of KGX_FA_FINISHED over text[0, e) -- the records complete before e,
+ * then the record in progress as it stands, an empty id included --
+ * consumed = n, newlines counts the whole text and error_newlines counts '\n'
+ * in text[0, e].  KGX_FA_STRICT without an offending byte changes nothing.
+ * The error's id is the last sequence's under KGX_FA_STRICT.  A caller that
+ * parses a file in parts reports the line 1 + (the `newlines` of the earlier
+ * calls) + error_newlines.
+ *
+ * residues, seq_offsets, ids and id_offsets are buffers of the context kept
+ * for this call alone (seq_offsets[0] = id_offsets[0] = 0): they are valid
+ * until the context's next kgx_fa_parse* call, across fq calls and across
+ * kgx_run_device(ctx, params, residues, seq_offsets, n_seqs, n_residues, ..)
+ * on the same context in particular.  residues and ids are followed by 16
+ * allocated bytes each; nothing past residues[n_residues), ids[n_id_bytes)
+ * and the offsets' [n_seqs + 1] is defined.  d_text is device memory aligned
+ * to 16 bytes, of n bytes and no more; n is at most KGX_FA_PARSE_MAX (byte
+ * positions and the sums over them are 32-bit on the device), KGX_ERANGE above
+ * it, checked before anything is allocated.  n = 0 gives zero sequences and
+ * null arrays without KGX_FA_FINISHED, and with it one empty record, both
+ * offset arrays {0, 0}.  KGX_EINVAL for a null argument, an unaligned d_text
+ * or an unknown flag; KGX_EDEVICE when the device's sums exceed what the text
+ * allows.  Synchronous. */
+#define KGX_FA_STRICT 1u   /* the first offending byte ends the parse (validate_fasta.cc:35-40) */
+#define KGX_FA_FINISHED 2u /* the text ends the input (parse_complete) */
+#define KGX_FA_PARSE_MAX 0xFFFFF000ull
+typedef struct kgx_fa_seqs {
+    uint32_t n_seqs, n_seqs_no_id;
+    uint64_t n_residues, n_id_bytes;
+    const uint8_t *residues;     /* device: what kgx_run_device takes */
+    const uint64_t *seq_offsets; /* device: [n_seqs + 1] */
+    const uint8_t *ids;          /* device */
+    const uint64_t *id_offsets;  /* device: [n_seqs + 1] */
+    uint64_t consumed;           /* the caller feeds text[consumed, n) again, in front of what comes next */
+    uint64_t newlines;           /* '\n' in text[0, consumed) */
+    uint32_t error;              /* 0 none, 1 missing '>', 2 bad data character, 3 bad id or data character */
+    uint32_t error_byte;
+    uint64_t error_pos, error_newlines; /* the first offending byte; '\n' in text[0, error_pos] */
+    float upload_ms, parse_ms;          /* event times */
+} kgx_fa_seqs;
+int kgx_fa_parse_device(kgx_ctx *ctx, const void *d_text, uint64_t n, uint32_t flags, kgx_fa_seqs *out);
+/* host text: uploaded (by DMA straight from pinned memory, kgx_host_alloc;
+ * otherwise through the context's staging), then the above */
+int kgx_fa_parse(kgx_ctx *ctx, const char *text, uint64_t n, uint32_t flags, kgx_fa_seqs *out);
+
 /* The tool as a streaming handle: FASTQ text in, FASTA text out.  Blocks may
  * cut a record anywhere; `finished` ends the file and resets the parser and
  * the error state for the next one.  Records are framed as the fq handler
