@@ -227,6 +227,12 @@ class FqReads(ctypes.Structure):
         return t + chr(self.error_byte) + "'" if self.error == 3 else t
 
 
+class FqIds(ctypes.Structure):
+    """kgx_fq_ids: the ids of chosen reads of a device parse, on the host."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_bytes", ctypes.c_uint64), ("ids", ctypes.c_void_p),
+                ("id_offsets", ctypes.c_void_p)]
+
+
 FA_STRICT, FA_FINISHED = 1, 2  # KGX_FA_STRICT, KGX_FA_FINISHED
 FA_PARSE_MAX = 0xFFFFF000      # KGX_FA_PARSE_MAX
 # kgx_fa_seqs.error -> the reference's wording (fasta_parser.h:54-132); 2 and 3 are followed by the byte and "'"
@@ -370,6 +376,10 @@ SIGNATURES = {
     "kgx_fq_parse": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
     "kgx_fq_parse_device": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FqReads)]),
     "kgx_fq_proteins_device": (_INT, [_P, ctypes.POINTER(FqReads), ctypes.POINTER(FqText)]),
+    "kgx_fq_read_ids": (_INT, [_P, ctypes.POINTER(FqReads), _P, _U32, ctypes.POINTER(FqIds)]),
+    "kgx_fq_stat": (_INT, [_P, _CS, ctypes.POINTER(_U64)]),
+    "kgx_ctx_get_option": (_INT, [_P, _CS, ctypes.POINTER(ctypes.c_int64)]),
+    "kgx_ctx_memcpy_d2d": (_INT, [_P, _P, _P, _U64]),
     "kgx_fa_parse": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FaSeqs)]),
     "kgx_fa_parse_device": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(FaSeqs)]),
     "kgx_f2p_create": (_INT, [_P, _U64, _PP]),
@@ -958,6 +968,19 @@ class Context:
               "kgx_fq_proteins_device")
         return t
 
+    def fq_read_ids(self, reads: FqReads, index) -> dict:
+        """kgx_fq_read_ids: the ids of the reads `index` names (strictly ascending) of the last
+        fq_parse's reads, gathered on the device: {"n", "ids" (uint8), "id_offsets" (uint64, n + 1)}."""
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        out = FqIds()
+        check(lib().kgx_fq_read_ids(self.handle, ctypes.byref(reads), idx.ctypes.data if idx.size else None,
+                                    idx.size, ctypes.byref(out)), "kgx_fq_read_ids")
+        off = np.ctypeslib.as_array(ctypes.cast(out.id_offsets, ctypes.POINTER(ctypes.c_uint64)),
+                                    (out.n + 1,)).copy()
+        ids = (np.ctypeslib.as_array(ctypes.cast(out.ids, ctypes.POINTER(ctypes.c_uint8)), (out.n_bytes,)).copy()
+               if out.n_bytes else np.zeros(0, np.uint8))
+        return {"n": int(out.n), "ids": ids, "id_offsets": off}
+
     def fq_reads_to_host(self, r: FqReads, arrays=("bases", "read_offsets", "ids", "id_offsets")) -> dict:
         """Host copies of a kgx_fq_reads' arrays (tests / tools)."""
         out = {"bases": np.zeros(r.n_bases, np.uint8), "read_offsets": np.zeros(r.n_reads + 1, np.uint64),
@@ -1034,6 +1057,11 @@ class Context:
 
     def set_option(self, name: str, value: int) -> None:
         check(lib().kgx_ctx_set_option(self.handle, name.encode(), value), f"set_option({name})")
+
+    def get_option(self, name: str) -> int:
+        v = ctypes.c_int64()
+        check(lib().kgx_ctx_get_option(self.handle, name.encode(), ctypes.byref(v)), f"get_option({name})")
+        return v.value
 
     def synchronize(self) -> None:
         check(lib().kgx_ctx_synchronize(self.handle), "kgx_ctx_synchronize")
@@ -1306,6 +1334,12 @@ class FqHandler:
         check(lib().kgx_fq_process(self.handle, fastq, len(fastq), int(finished), ctypes.byref(t),
                                    ctypes.byref(n)), "kgx_fq_process")
         return ctypes.string_at(t, n.value) if n.value else b""
+
+    def stat(self, name: str) -> int:
+        """kgx_fq_stat: a counter of the handler since its creation."""
+        v = ctypes.c_uint64()
+        check(lib().kgx_fq_stat(self.handle, name.encode(), ctypes.byref(v)), "kgx_fq_stat")
+        return v.value
 
     def close(self) -> None:
         if self.handle:

@@ -32,13 +32,14 @@ ARCH = "gfx950"
 
 LIB_SOURCES = ["kgx_plan.hip", "kgx_probe.hip", "kgx_line_index.hip", "kgx_score.hip", "kgx_gather.hip",
                "kgx_fused.hip", "kgx_synth.hip", "kgx_tables.hip", "kgx_fq.hip", "kgx_fq_parse.hip", "kgx_fa_parse.hip",
-               "kgx_sig.hip",
+               "kgx_fq_ids.hip", "kgx_sig.hip",
                "kgx_recall.hip", "kgx_uniq.hip", "kgx_inflate.hip", "kgx_runtime.cpp", "kgx_gunzip.cpp",
                "kgx_host_batch.cpp", "kgx_pool.cpp", "kgx_svc.cpp", "kguts_hip.cpp", "kguts_mapping.cpp",
                "kguts_lookup.cpp", "kguts_fq.cpp", "kgx_handlers.cpp", "kgx_f2p.cpp"]
 HEADERS = ["kgx_internal.h", "kgx_device.h", "kgx_line_home.h", "kguts_hip.h", "kguts_impl.h", "kgx_rt.h", "kgx_lstd.h", "kgx_handlers.h",
            "kgx_wave_sort.h", "kgx_options.h", "kgx_dispatch.h", "kgx_score_map.h", "kgx_sig_plan.h",
-           "kgx_inflate.h", "kgx_gzip.h", "kgx_tiled.h", "kgx_fq_parse.h", "kgx_fq_parts.h", "kgx_text_scan.h"]
+           "kgx_inflate.h", "kgx_gzip.h", "kgx_tiled.h", "kgx_fq_parse.h", "kgx_fq_parts.h", "kgx_fq_body.h",
+           "kgx_text_scan.h"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{CSRC}",
           "-Wall", "-Wno-unused-function"]
 

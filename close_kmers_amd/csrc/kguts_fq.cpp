@@ -5,9 +5,15 @@
  * kgx_gzip.h), is cut into parts that are parsed ahead on worker threads
  * (FqParts); the parts rotate over three contexts (process_text), and each
  * part's reads get their frame chosen on the host (finish_block,
- * choose_frame).
+ * choose_frame).  With the context's option "fq_body_device" at 1 when a
+ * request starts, the parts are framed on the device instead (DeviceBody,
+ * DESIGN.md §8.14): plain byte cuts, the text behind a part's last complete
+ * record carried in front of the next, a gzip body's blocked members inflated
+ * on the device into the text the parser reads, and only the ids of the reads
+ * that are printed brought down.
  */
 #include "kguts_impl.h"
+#include "kgx_fq_body.h"  /* FqBodyParts: the parts of a block the device frames */
 #include "kgx_fq_parse.h" /* fq_parse: FastqParser::parse_char as the fq handler drives it */
 #include "kgx_gzip.h"
 
@@ -17,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <numeric>
 #include <sstream>
 #include <thread>
 
@@ -46,6 +53,13 @@ const char *fq_cut_after(const char *p, const char *end)
         p = l0;
     }
     return nullptr;
+}
+
+/* KGX_FQ_PART_KB: the part size, for tests of the parts (default 32 MB, at least 4 KB) */
+size_t fq_part_bytes()
+{
+    const char *e = std::getenv("KGX_FQ_PART_KB");
+    return e ? std::max<size_t>(4, std::strtoull(e, nullptr, 10)) << 10 : size_t(32) << 20;
 }
 
 double ms_since(std::chrono::steady_clock::time_point t0)
@@ -100,6 +114,14 @@ struct FqRequest::FqPart {
         id_chars.clear();
     }
     void parse(const char *a, const char *b) { fq_parse(a, b, state, id, bases, len, roff, id_chars, id_off); }
+    /* parse_complete(): the record in progress is emitted as it stands */
+    void complete()
+    {
+        id_chars += id;
+        id_off.push_back(id_chars.size());
+        roff.push_back(len);
+        id.clear();
+    }
     /* the parse stands at a record start with nothing pending */
     bool at_record_start() const { return state == FQ_START && id.empty() && len == roff.back(); }
     FqBlock view() const
@@ -167,11 +189,7 @@ private:
 
 void FqRequest::FqParts::open(const char *text, size_t n, bool finished)
 {
-    /* KGX_FQ_PART_KB: the part size, for tests of the parallel parse */
-    const size_t kPartBytes = [] {
-        const char *e = std::getenv("KGX_FQ_PART_KB");
-        return e ? std::max<size_t>(4, std::strtoull(e, nullptr, 10)) << 10 : size_t(32) << 20;
-    }();
+    const size_t kPartBytes = fq_part_bytes();
     end_ = text + n;
     finished_ = finished;
     cuts_.assign(1, text);
@@ -264,10 +282,7 @@ void FqRequest::FqParts::close()
 void FqRequest::FqParts::finish_part(FqPart &pt)
 {
     if (finished_) { /* parse_complete() emits the last record */
-        pt.id_chars += pt.id;
-        pt.id_off.push_back(pt.id_chars.size());
-        pt.roff.push_back(pt.len);
-        pt.id.clear();
+        pt.complete();
         rq_.state_ = FQ_START;
         rq_.id_.clear();
         rq_.seq_.clear();
@@ -324,6 +339,135 @@ void FqRequest::FqParts::release(size_t j)
     cv_.notify_all();
 }
 
+/* ---- option "fq_body_device": parts framed on the device -------------------- */
+
+/* What the device-framed path keeps between parts and blocks.  The carried
+ * text -- parts.have() bytes behind the last complete record -- is in `part`
+ * (a text body) or in d_text[cur] at tail_off (a gzip body, whose text never
+ * comes down but for the request's last incomplete record). */
+struct FqRequest::DeviceBody {
+    FqBodyParts parts;
+    int device = 0;
+    char *part = nullptr; /* a part's text on the host, pinned (kgx_host_alloc): carried text, then new bytes */
+    size_t part_cap = 0;
+    void *d_gz = nullptr; /* a gzip block's compressed bytes */
+    size_t d_gz_cap = 0;
+    char *d_text[2] = {nullptr, nullptr}; /* a gzip body's parts alternate: the carry is copied from one to the other */
+    size_t d_text_cap[2] = {0, 0};
+    int cur = 0;
+    uint64_t tail_off = 0;
+    bool tail_on_device = false;
+    FqPart host_part; /* a part the host parser makes: a request's end, a record too long for the device */
+
+    DeviceBody() = default;
+    DeviceBody(const DeviceBody &) = delete;
+    DeviceBody &operator=(const DeviceBody &) = delete;
+    ~DeviceBody()
+    {
+        if (part)
+            kgx_host_free(part);
+        for (void *p : {d_gz, (void *)d_text[0], (void *)d_text[1]})
+            if (p)
+                kgx_device_free(p);
+    }
+    void forget()
+    {
+        parts.forget();
+        tail_on_device = false;
+        tail_off = 0;
+    }
+    /* `part` holds need bytes; its first `keep` stay */
+    void host_room(size_t need, size_t keep)
+    {
+        if (need <= part_cap)
+            return;
+        void *q = nullptr;
+        const size_t want = need + need / 4 + 4096;
+        if (int rc = kgx_host_alloc(want, &q))
+            throw_last(rc, "kgx_host_alloc");
+        if (keep)
+            std::memcpy(q, part, keep);
+        if (part)
+            kgx_host_free(part);
+        part = static_cast<char *>(q);
+        part_cap = want;
+    }
+    /* a device buffer of at least need bytes; what it held is not kept */
+    void device_room(void **p, size_t *cap, size_t need)
+    {
+        if (need <= *cap)
+            return;
+        if (*p)
+            kgx_device_free(*p);
+        *p = nullptr;
+        *cap = 0;
+        const size_t want = need + need / 4 + 4096;
+        if (int rc = kgx_device_alloc(device, want, p))
+            throw_last(rc, "kgx_device_alloc");
+        *cap = want;
+    }
+    /* the carried text into `part` (a request's end; a plain member's text behind blocked ones) */
+    void tail_to_host()
+    {
+        if (!tail_on_device)
+            return;
+        const uint64_t have = parts.have();
+        if (have) {
+            host_room((size_t)have, 0);
+            if (int rc = kgx_memcpy_d2h(part, d_text[cur] + tail_off, have))
+                throw_last(rc, "kgx_memcpy_d2h");
+        }
+        tail_on_device = false;
+        tail_off = 0;
+    }
+    /* part[0, total) through the host parser from the start state: its
+     * complete records, and with `finished` the record in progress
+     * (parse_complete), as host_part; what follows the last complete record
+     * is carried otherwise.  Null when that makes no read. */
+    FqPart *host_rest(size_t total, bool finished)
+    {
+        host_part.begin(total, FQ_START, std::string(), nullptr, 0);
+        size_t consumed = 0;
+        const char *p = part, *end = part + total;
+        while (p < end) { /* line by line: where the last complete record ends */
+            const char *nl = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
+            const char *q = nl ? nl + 1 : end;
+            const size_t before = host_part.roff.size();
+            host_part.parse(p, q);
+            if (host_part.roff.size() != before)
+                consumed = (size_t)(q - part);
+            p = q;
+        }
+        if (finished) {
+            host_part.complete();
+            forget();
+        } else {
+            if (consumed && total > consumed)
+                std::memmove(part, part + consumed, total - consumed);
+            parts.carried(total - consumed);
+            tail_on_device = false;
+        }
+        return host_part.roff.size() > 1 ? &host_part : nullptr;
+    }
+};
+
+/* a part of a block as the rotation takes it: reads the device framed, or a
+ * part the host parser made */
+struct FqRequest::DevicePart {
+    kgx_fq_reads reads{};
+    FqPart *host = nullptr;
+};
+
+FqRequest::DeviceBody &FqRequest::device_body()
+{
+    if (!dev_) {
+        dev_.reset(new DeviceBody);
+        dev_->device = kgx_image_device(kg_.image_->handle());
+        dev_->parts.reset(fq_part_bytes(), KGX_FQ_PARSE_MAX);
+    }
+    return *dev_;
+}
+
 /* ---- FqRequest -------------------------------------------------------------- */
 
 FqRequest::FqRequest(KmerGuts &kg, std::shared_ptr<KmerPegMapping> mapping)
@@ -345,21 +489,321 @@ void FqRequest::process(const std::string &block, bool finished, std::ostream &o
 
 void FqRequest::process(const char *block, size_t n, bool finished, std::ostream &os)
 {
-    const bool fresh = state_ == FQ_START && id_.empty() && seq_.empty();
+    const bool fresh = state_ == FQ_START && id_.empty() && seq_.empty() && !(dev_ && dev_->parts.have());
+    if (fresh && body_->body() == GZ_BODY_UNKNOWN) { /* a request starts: its choice holds to its end */
+        int64_t v = 0;
+        if (int rc = kgx_ctx_get_option(kg_.ctx(), "fq_body_device", &v))
+            throw_last(rc, "kgx_ctx_get_option");
+        body_device_ = v != 0;
+    }
     const char *text = nullptr;
     size_t len = 0;
-    if (int rc = body_->feed(kg_.ctx(), block, n, finished, fresh, &text, &len)) {
+    bool listed = false;
+    if (int rc = body_device_ ? body_->feed_listed(kg_.ctx(), block, n, finished, fresh, &text, &len, &listed)
+                              : body_->feed(kg_.ctx(), block, n, finished, fresh, &text, &len)) {
         /* bad gzip data: the parser forgets the request too */
         state_ = FQ_START;
         id_.clear();
         seq_.clear();
+        if (dev_)
+            dev_->forget();
         throw_last(rc, "kgx_gunzip");
     }
-    if (!text) /* held: too short to tell text from gzip yet */
+    if (!body_device_) {
+        if (!text) /* held: too short to tell text from gzip yet */
+            return;
+        if (body_->gzip() && !len && !finished) /* no complete member yet */
+            return;
+        if (body_->gzip())
+            stats_.host_members += body_->last_members();
+        process_text(text, len, finished, os);
         return;
-    if (body_->gzip() && !len && !finished) /* no complete member yet */
+    }
+    try {
+        if (listed) { /* blocked members: inflated on the device, part by part */
+            process_members_device(finished, os);
+        } else if (text && !(body_->gzip() && !len && !finished)) {
+            if (body_->gzip())
+                stats_.host_members += body_->last_members();
+            process_text_device(text, len, finished, os);
+        }
+    } catch (...) { /* the request is forgotten: the next block starts one */
+        body_->reset();
+        if (dev_)
+            dev_->forget();
+        throw;
+    }
+}
+
+/* ---- option "fq_body_device": the parts' rotation and sources ------------- */
+
+namespace {
+
+/* memcpy by a few threads for a part's 32 MB */
+void copy_bytes(char *dst, const char *src, size_t n)
+{
+    const size_t T = std::min<size_t>(4, n >> 23);
+    if (T <= 1) {
+        std::memcpy(dst, src, n);
         return;
-    process_text(text, len, finished, os);
+    }
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < T; t++)
+        pool.emplace_back([=] { std::memcpy(dst + n * t / T, src + n * t / T, n * (t + 1) / T - n * t / T); });
+    for (auto &th : pool)
+        th.join();
+}
+
+/* a record ends with its fourth newline at the earliest: a short text with
+ * fewer holds no complete record and need not go to the device (a request
+ * that arrives in blocks of a few bytes) */
+bool may_hold_record(const char *text, size_t n)
+{
+    if (n > 65536)
+        return true;
+    return std::count(text, text + n, '\n') >= 4;
+}
+
+}  // namespace
+
+/* the fragment pass over reads where kgx_fq_parse left them, enqueued: what
+ * upload_block does for reads the host parsed */
+FqRequest::FqLaunched FqRequest::start_device(const kgx_fq_reads &reads, kgx_ctx *ctx)
+{
+    FqLaunched l;
+    l.ctx = ctx;
+    l.n_reads = reads.n_reads;
+    if (l.n_reads == 0)
+        return l;
+    int rc = kgx_ctx_set_option(ctx, "fq_residues", 0);
+    if (rc)
+        throw_last(rc, "kgx_ctx_set_option");
+    if ((rc = kgx_fq_fragments_device_start(ctx, reads.bases, reads.read_offsets, reads.n_reads, reads.n_bases)))
+        throw_last(rc, "kgx_fq_fragments_device_start");
+    return l;
+}
+
+/* process_text's rotation over the parts `next` hands out: part k + 2 is
+ * framed on its context and its fragment pass enqueued while part k + 1's
+ * lookup is launched and part k is collected.  One FamilyMapper for the
+ * block. */
+void FqRequest::run_device_parts(const std::function<bool(kgx_ctx *, DevicePart &)> &next, std::ostream &os)
+{
+    const bool timing = std::getenv("KGX_FQ_TIMING") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    FamilyMapper mapper(kg_, mapping_);
+    double device_ms = 0.0, frame_ms = 0.0;
+    struct Slot {
+        DevicePart p;
+        FqLaunched l;
+    } sl[3];
+    size_t have = 0;
+    bool last = false; /* `next` has no further part */
+    auto prepare = [&]() {
+        Slot &s = sl[have % 3];
+        kgx_ctx *ctx = rotation_ctx(have % 3);
+        s.p = DevicePart{};
+        const auto p0 = std::chrono::steady_clock::now();
+        if (!next(ctx, s.p)) {
+            last = true;
+            frame_ms += ms_since(p0);
+            return;
+        }
+        s.l = s.p.host ? upload_block(s.p.host->view(), ctx) : start_device(s.p.reads, ctx);
+        frame_ms += ms_since(p0);
+        stats_.reads += s.l.n_reads;
+        have++;
+    };
+    auto launch = [&](Slot &s) {
+        const auto l0 = std::chrono::steady_clock::now();
+        launch_uploaded(s.l);
+        device_ms += ms_since(l0);
+    };
+    prepare();
+    if (have)
+        launch(sl[0]);
+    if (!last)
+        prepare();
+    for (size_t k = 0; k < have; k++) {
+        if (k + 1 < have) {
+            if (!last)
+                prepare();
+            launch(sl[(k + 1) % 3]);
+        }
+        Slot &cur = sl[k % 3];
+        FqBlock blk;
+        if (cur.p.host) {
+            blk = cur.p.host->view();
+        } else {
+            blk.n = cur.p.reads.n_reads;
+            blk.device_reads = &cur.p.reads;
+        }
+        const auto f0 = std::chrono::steady_clock::now();
+        finish_block(blk, cur.l, mapper, os);
+        device_ms += ms_since(f0);
+    }
+    if (timing)
+        std::fprintf(stderr, "[fq] block in %zu part(s), framed on the device: %.3f ms, framing %.3f ms, device + "
+                             "frame choice %.3f ms\n",
+                     have, ms_since(t0), frame_ms, device_ms);
+}
+
+void FqRequest::process_text_device(const char *text, size_t n, bool finished, std::ostream &os)
+{
+    DeviceBody &d = device_body();
+    d.tail_to_host();
+    d.parts.begin_block(n, fq_part_bytes());
+    size_t pos = 0;
+    bool rest_done = false;
+    auto next = [&](kgx_ctx *ctx, DevicePart &out) -> bool {
+        while (pos < n && !d.parts.beyond_limit(n - pos)) {
+            const uint64_t kept = d.parts.have(), k = d.parts.take(n - pos);
+            d.host_room((size_t)(kept + k), (size_t)kept);
+            copy_bytes(d.part + kept, text + pos, (size_t)k);
+            d.parts.took(k);
+            pos += (size_t)k;
+            const uint64_t have = d.parts.have();
+            kgx_fq_reads r{};
+            if (may_hold_record(d.part, (size_t)have)) {
+                if (int rc = kgx_fq_parse(ctx, d.part, have, 0, &r))
+                    throw_last(rc, "kgx_fq_parse");
+                stats_.device_parts++;
+            }
+            if (r.consumed && have > r.consumed)
+                std::memmove(d.part, d.part + r.consumed, (size_t)(have - r.consumed));
+            d.parts.parsed(r.consumed, n - pos);
+            stats_.tail_bytes_max = std::max(stats_.tail_bytes_max, d.parts.have());
+            if (r.n_reads) {
+                out.reads = r;
+                return true;
+            }
+        }
+        if (rest_done)
+            return false;
+        rest_done = true;
+        /* a record too long for one parse: the rest of the block on the host;
+         * the request's end: what the last complete record left */
+        if (pos == n && !(finished && d.parts.have()))
+            return false;
+        const uint64_t kept = d.parts.have();
+        d.host_room((size_t)(kept + (n - pos)), (size_t)kept);
+        copy_bytes(d.part + kept, text + pos, n - pos);
+        const size_t total = (size_t)kept + (n - pos);
+        pos = n;
+        stats_.host_parts++;
+        out.host = d.host_rest(total, finished);
+        return out.host != nullptr;
+    };
+    run_device_parts(next, os);
+    if (finished)
+        d.forget();
+}
+
+void FqRequest::process_members_device(bool finished, std::ostream &os)
+{
+    DeviceBody &d = device_body();
+    GzipBodyReader &body = *body_;
+    const std::vector<GzipListed> &list = body.list();
+    const size_t n = list.size();
+    std::vector<uint32_t> out_len(n);
+    uint64_t text_bytes = 0;
+    for (size_t i = 0; i < n; i++)
+        text_bytes += out_len[i] = list[i].out_len;
+    /* the compressed bytes go up once */
+    d.device_room(&d.d_gz, &d.d_gz_cap, body.compressed_len());
+    if (int rc = kgx_memcpy_h2d(d.d_gz, body.compressed(), body.compressed_len()))
+        throw_last(rc, "kgx_memcpy_h2d");
+    d.parts.begin_block(text_bytes, fq_part_bytes());
+    size_t i = 0;
+    bool rest_done = false, on_host = false;
+    auto next = [&](kgx_ctx *ctx, DevicePart &out) -> bool {
+        while (i < n) {
+            uint64_t bytes = 0;
+            const uint32_t k = d.parts.take_members(&out_len[i], (uint32_t)std::min<size_t>(n - i, UINT32_MAX), &bytes);
+            if (d.parts.members_beyond_limit(bytes))
+                break;
+            /* the carry to the front of the other buffer, the members behind it */
+            const uint64_t kept = d.parts.have();
+            const int dst = d.cur ^ 1;
+            void *q = d.d_text[dst];
+            d.device_room(&q, &d.d_text_cap[dst], (size_t)(kept + bytes) + 16);
+            d.d_text[dst] = static_cast<char *>(q);
+            if (kept) {
+                const int rc = d.tail_on_device
+                                   ? kgx_ctx_memcpy_d2d(ctx, d.d_text[dst], d.d_text[d.cur] + d.tail_off, kept)
+                                   : kgx_memcpy_h2d(d.d_text[dst], d.part, kept);
+                if (rc)
+                    throw_last(rc, "carried text");
+            }
+            if (int rc = body.inflate_listed(ctx, d.d_gz, (uint32_t)i, k, d.d_text[dst], kept))
+                throw_last(rc, "kgx_gunzip");
+            stats_.device_members += k;
+            i += k;
+            d.parts.took(bytes);
+            d.cur = dst;
+            d.tail_off = 0;
+            d.tail_on_device = true;
+            kgx_fq_reads r{};
+            if (bytes) {
+                if (int rc = kgx_fq_parse_device(ctx, d.d_text[dst], kept + bytes, 0, &r))
+                    throw_last(rc, "kgx_fq_parse_device");
+                stats_.device_parts++;
+            }
+            d.tail_off = r.consumed;
+            d.parts.parsed(r.consumed, n - i);
+            stats_.tail_bytes_max = std::max(stats_.tail_bytes_max, d.parts.have());
+            if (r.n_reads) {
+                out.reads = r;
+                return true;
+            }
+        }
+        if (rest_done)
+            return false;
+        rest_done = true;
+        if (i == n && !(finished && d.parts.have()))
+            return false;
+        d.tail_to_host(); /* the one download of a request's carried text */
+        const uint64_t kept = d.parts.have();
+        size_t total = (size_t)kept;
+        if (i < n) { /* a record too long for one parse: the block's members again, on the host */
+            const uint64_t skip = list[i].out_off;
+            const char *text = nullptr;
+            size_t len = 0;
+            on_host = true;
+            if (int rc = body.inflate_listed_on_host(kg_.ctx(), finished, &text, &len))
+                throw_last(rc, "kgx_gunzip");
+            stats_.host_members += body.last_members();
+            d.host_room((size_t)kept + (len - (size_t)skip), (size_t)kept);
+            copy_bytes(d.part + kept, text + skip, len - (size_t)skip);
+            total += len - (size_t)skip;
+            i = n;
+        }
+        stats_.host_parts++;
+        out.host = d.host_rest(total, finished);
+        return out.host != nullptr;
+    };
+    run_device_parts(next, os);
+    if (!on_host)
+        body.listed_done(finished);
+    if (finished)
+        d.forget();
+}
+
+bool FqRequest::stat(const char *name, uint64_t *value) const
+{
+    const struct {
+        const char *name;
+        uint64_t v;
+    } all[] = {{"device_parts", stats_.device_parts},     {"host_parts", stats_.host_parts},
+               {"device_members", stats_.device_members}, {"host_members", stats_.host_members},
+               {"ids_fetched", stats_.ids_fetched},       {"reads", stats_.reads},
+               {"tail_bytes_max", stats_.tail_bytes_max}};
+    for (const auto &s : all)
+        if (!std::strcmp(s.name, name)) {
+            *value = s.v;
+            return true;
+        }
+    return false;
 }
 
 kgx_ctx *FqRequest::rotation_ctx(size_t i)
@@ -400,6 +844,8 @@ void FqRequest::process_text(const char *text, size_t n, bool finished, std::ost
         Slot &s = sl[have % 3];
         s.pt = &src.get(have, have ? sl[(have - 1) % 3].pt : nullptr, &last);
         s.l = upload_block(s.pt->view(), rotation_ctx(have % 3));
+        stats_.host_parts++;
+        stats_.reads += s.l.n_reads;
         have++;
     };
     auto launch = [&](Slot &s) {
@@ -451,6 +897,8 @@ void FqRequest::process_reads(const std::vector<std::pair<std::string, std::stri
         pt.roff.push_back(pt.len);
     }
     FamilyMapper mapper(kg_, mapping_);
+    stats_.host_parts++;
+    stats_.reads += reads.size();
     process_block(pt.view(), mapper, os);
 }
 
@@ -623,14 +1071,36 @@ void FqRequest::finish_block(const FqBlock &blk, FqLaunched &l, FamilyMapper &ma
             throw_last(rc, "kgx_fq_called_reads");
         mark("collect");
         const FrameView view{cr.call_offsets, cr.calls, nullptr, nullptr, cr.frag_len, nullptr, nullptr};
+        /* a device-framed part: the ids of these reads alone come down, in their order */
+        FqBlock ids = blk;
+        if (blk.device_reads) {
+            kgx_fq_ids got;
+            if ((rc = kgx_fq_read_ids(ctx, blk.device_reads, cr.reads, cr.n, &got)))
+                throw_last(rc, "kgx_fq_read_ids");
+            stats_.ids_fetched += cr.n;
+            ids.ids = got.ids;
+            ids.id_off = got.id_offsets;
+        }
         for (uint32_t i = 0; i < cr.n; i++) {
-            const uint32_t r = cr.reads[i];
-            if (blk.id_len(r))
-                choose_frame(view, cr.frag_offsets[i], cr.frame_counts + (size_t)i * 6, blk.id(r), blk.id_len(r), mapper,
+            const size_t r = blk.device_reads ? i : cr.reads[i];
+            if (ids.id_len(r))
+                choose_frame(view, cr.frag_offsets[i], cr.frame_counts + (size_t)i * 6, ids.id(r), ids.id_len(r), mapper,
                              scratch, os);
         }
         mark("host loop");
         return;
+    }
+    /* every read with an id is replayed: a device-framed part's ids all come down */
+    FqBlock ids = blk;
+    if (blk.device_reads) {
+        std::vector<uint32_t> all(n_reads);
+        std::iota(all.begin(), all.end(), 0u);
+        kgx_fq_ids got;
+        if ((rc = kgx_fq_read_ids(ctx, blk.device_reads, all.data(), n_reads, &got)))
+            throw_last(rc, "kgx_fq_read_ids");
+        stats_.ids_fetched += n_reads;
+        ids.ids = got.ids;
+        ids.id_off = got.id_offsets;
     }
     /* fragments per (read, frame): fragment g of read r, frame slot k */
     std::vector<uint32_t> fcount((size_t)n_reads * 6);
@@ -668,8 +1138,8 @@ void FqRequest::finish_block(const FqBlock &blk, FqLaunched &l, FamilyMapper &ma
                          frag_off.empty() ? nullptr : frag_off.data(), fr.offsets};
     /* reads in order, every one with an id */
     for (uint32_t r = 0; r < n_reads; r++)
-        if (blk.id_len(r))
-            choose_frame(view, rfirst[r], &fcount[(size_t)r * 6], blk.id(r), blk.id_len(r), mapper, scratch, os);
+        if (ids.id_len(r))
+            choose_frame(view, rfirst[r], &fcount[(size_t)r * 6], ids.id(r), ids.id_len(r), mapper, scratch, os);
     mark("host loop");
 }
 
@@ -717,6 +1187,15 @@ int kgx_fq_create(kgx_image *img, const char *data_dir, const char *genus_file, 
 int kgx_fq_destroy(kgx_fq *q)
 {
     delete q;
+    return KGX_OK;
+}
+
+int kgx_fq_stat(kgx_fq *q, const char *name, uint64_t *value)
+{
+    if (!q || !name || !value)
+        return kgx::fail(KGX_EINVAL, "null argument");
+    if (!q->req->stat(name, value))
+        return kgx::fail(KGX_EINVAL, std::string("unknown statistic ") + name);
     return KGX_OK;
 }
 

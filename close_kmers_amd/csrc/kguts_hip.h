@@ -575,6 +575,8 @@ public:
     void process(const char *fastq_block, size_t n, bool finished, std::ostream &os);
     /* reads already parsed (id, DNA) */
     void process_reads(const std::vector<std::pair<std::string, std::string>> &reads, std::ostream &os);
+    /* a counter since construction (include/kgx.h kgx_fq_stat); false for an unknown name */
+    bool stat(const char *name, uint64_t *value) const;
 
 private:
     /* parsed reads, flat (a view): read r's id is ids[id_off[r], id_off[r+1]),
@@ -589,6 +591,10 @@ private:
         size_t n_reads() const { return n; }
         const char *id(size_t r) const { return ids + id_off[r]; }
         size_t id_len(size_t r) const { return (size_t)(id_off[r + 1] - id_off[r]); }
+        /* a part framed on the device (option "fq_body_device"): ids and
+         * id_off are null, and finish_block fetches the ids of the reads it
+         * prints from the parse's buffers (kgx_fq_read_ids) */
+        const kgx_fq_reads *device_reads = nullptr;
     };
     /* one part of a block, parsed, and the source of a block's parts: the
      * cuts, the parallel parse ahead and its pinned buffers (kguts_fq.cpp) */
@@ -626,6 +632,24 @@ private:
     std::string id_, seq_;
     std::unique_ptr<FqParts> parts_; /* kept across blocks: its pinned buffers are reused */
     std::unique_ptr<GzipBodyReader> body_; /* text or gzip: the sniff and the inflate (kgx_gzip.h) */
+    /* option "fq_body_device" (kguts_fq.cpp): the request's choice, made when
+     * it starts, and what the device-framed path keeps -- the part buffers,
+     * the carried text, on the host or on the device */
+    struct DeviceBody;
+    bool body_device_ = false;
+    std::unique_ptr<DeviceBody> dev_;
+    DeviceBody &device_body();
+    /* a block of a text body / of a gzip body whose members are listed */
+    void process_text_device(const char *text, size_t n, bool finished, std::ostream &os);
+    void process_members_device(bool finished, std::ostream &os);
+    /* the rotation of process_text over parts `next` hands out */
+    struct DevicePart;
+    void run_device_parts(const std::function<bool(kgx_ctx *, DevicePart &)> &next, std::ostream &os);
+    FqLaunched start_device(const kgx_fq_reads &reads, kgx_ctx *ctx);
+    struct Stats {
+        uint64_t device_parts = 0, host_parts = 0, device_members = 0, host_members = 0, ids_fetched = 0, reads = 0,
+                 tail_bytes_max = 0;
+    } stats_;
 };
 
 /* one host-buffer batch through kg's context, device results only (no D2H):

@@ -1426,6 +1426,7 @@ int kgx_fq_upload(kgx_ctx *c, const char *bases, const uint64_t *read_offsets, u
                                hipMemcpyHostToDevice, c->stream));
     }
     c->fq_up.active = true;
+    c->fp_last = kgx_fq_reads{}; /* a parse's reads are gone from fq_bases */
     c->fq_up.n_reads = n_reads;
     c->fq_up.n_bases = nb;
     return KGX_OK;

@@ -164,6 +164,7 @@ int fq_parse_device(kgx_ctx *c, const uint8_t *text, uint64_t n, uint32_t flags,
     hipStream_t st = c->stream;
     const uint32_t n_tiles = tiles_of(n);
     c->fq_parses++;
+    c->fp_last = kgx_fq_reads{};
     HIP_TRY(c->fp_map.reserve((uint64_t)n_tiles * 4));
     HIP_TRY(c->fp_state.reserve((uint64_t)n_tiles + 1));
     HIP_TRY(c->fp_lane.reserve((uint64_t)n_tiles * WG));
@@ -238,6 +239,7 @@ int fq_parse_device(kgx_ctx *c, const uint8_t *text, uint64_t n, uint32_t flags,
         out->error_pos = e;
         out->error_newlines = cut ? cut_newlines + (out->error_byte == '\n') : h[SUM_ERROR_NL];
     }
+    c->fp_last = *out;
     return KGX_OK;
 }
 
@@ -262,8 +264,10 @@ int kgx_fq_parse_device(kgx_ctx *c, const void *d_text, uint64_t n, uint32_t fla
 {
     if (int rc = parse_checks(c, d_text, n, flags, out))
         return rc;
-    if (!n)
+    if (!n) {
+        c->fp_last = kgx_fq_reads{};
         return KGX_OK;
+    }
     if (reinterpret_cast<uintptr_t>(d_text) & 15u)
         return fail(KGX_EINVAL, "kgx_fq_parse_device: d_text is not aligned to 16 bytes");
     return fq_parse_device(c, static_cast<const uint8_t *>(d_text), n, flags, out);
@@ -273,8 +277,10 @@ int kgx_fq_parse(kgx_ctx *c, const char *text, uint64_t n, uint32_t flags, kgx_f
 {
     if (int rc = parse_checks(c, text, n, flags, out))
         return rc;
-    if (!n)
+    if (!n) {
+        c->fp_last = kgx_fq_reads{};
         return KGX_OK;
+    }
     hipStream_t st = c->stream;
     HIP_TRY(c->fp_text.reserve(n));
     const bool pinned = host_pinned_range(text, n);

@@ -389,8 +389,93 @@ void GzipBodyReader::reset()
 int GzipBodyReader::feed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh, const char **text,
                          size_t *len)
 {
+    return feed_listed(ctx, block, n, finished, fresh, text, len, nullptr);
+}
+
+/* the complete members at the front of tail_, when all of them are blocked:
+ * list_ and list_len_ (empty: a plain member is among them, or there is none) */
+int GzipBodyReader::list_blocked(bool finished)
+{
+    list_.clear();
+    list_len_ = 0;
+    if (members_ && tail_.size() >= 2 && !((unsigned char)tail_[0] == 0x1f && (unsigned char)tail_[1] == 0x8b))
+        tail_.clear(); /* trailing bytes that are no gzip */
+    uint64_t members = 0, blocked = 0, out_bytes = 0, consumed = 0;
+    if (int rc = kgx_gunzip_scan(tail_.data(), tail_.size(), finished, &members, &blocked, &out_bytes, &consumed))
+        return rc;
+    if (members != blocked || !blocked)
+        return KGX_OK;
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(tail_.data());
+    uint64_t pos = 0, opos = 0;
+    for (uint64_t i = 0; i < blocked; i++) { /* the walk kgx_gunzip_scan has just made */
+        GzipHeader h;
+        uint32_t reason = 0;
+        GzipBlocked b;
+        if (gzip_header(p + pos, tail_.size() - pos, &h, &reason) != GZ_HDR_OK ||
+            gzip_blocked_extent(p + pos, tail_.size() - pos, h, &b) != 0)
+            return fail(KGX_EFORMAT, member_error(i, reason ? reason : (uint32_t)GZ_TRUNCATED, 0));
+        list_.push_back(GzipListed{pos + h.header_len, opos, b.data_len, b.isize, b.crc});
+        pos += b.total;
+        opos += b.isize;
+    }
+    list_len_ = (size_t)consumed; /* trailing bytes that are no gzip included */
+    return KGX_OK;
+}
+
+int GzipBodyReader::inflate_listed(kgx_ctx *ctx, const void *d_gz, uint32_t first, uint32_t count, void *d_out,
+                                   uint64_t out_base)
+{
+    if (!ctx || (uint64_t)first + count > list_.size() || (count && (!d_gz || !d_out)))
+        return fail(KGX_EINVAL, "inflate_listed: bad argument");
+    if (!count)
+        return KGX_OK;
+    HIP_TRY(hipSetDevice(ctx->img->device));
+    if (int rc = ensure_gz_events(ctx))
+        return rc;
+    std::vector<kgx_gz_member> m(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const GzipListed &l = list_[first + i];
+        m[i] = kgx_gz_member{l.in_off, out_base + (l.out_off - list_[first].out_off), l.in_len, l.out_len, l.crc, 0};
+    }
+    if (int rc = run_kernel(ctx, static_cast<const uint8_t *>(d_gz), m.data(), count, static_cast<uint8_t *>(d_out)))
+        return rc;
+    HIP_TRY(host_wait(ctx->stream));
+    for (uint32_t i = 0; i < count; i++)
+        if (ctx->h_gz_status[i].reason)
+            return fail(KGX_EFORMAT,
+                        member_error((uint64_t)first + i, ctx->h_gz_status[i].reason, ctx->h_gz_status[i].bit_pos));
+    return KGX_OK;
+}
+
+void GzipBodyReader::listed_done(bool finished)
+{
+    members_ += list_.size();
+    tail_.erase(0, list_len_);
+    list_.clear();
+    list_len_ = 0;
+    if (finished)
+        reset();
+}
+
+int GzipBodyReader::inflate_listed_on_host(kgx_ctx *ctx, bool finished, const char **text, size_t *len)
+{
+    list_.clear();
+    list_len_ = 0;
+    const int rc = inflate(ctx, finished, len);
+    *text = text_;
+    if (rc || finished)
+        reset();
+    return rc;
+}
+
+int GzipBodyReader::feed_listed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh,
+                                const char **text, size_t *len, bool *listed)
+{
     *text = nullptr;
     *len = 0;
+    last_members_ = 0;
+    if (listed)
+        *listed = false;
     bool joined = false;
     if (body_ == GZ_BODY_UNKNOWN || body_ == GZ_BODY_HELD) {
         body_ = gzip_sniff(tail_.data(), tail_.size(), block, n, finished, fresh);
@@ -404,7 +489,15 @@ int GzipBodyReader::feed(kgx_ctx *ctx, const char *block, size_t n, bool finishe
     int rc = KGX_OK;
     if (gzip_) {
         tail_.append(block, n);
-        rc = inflate(ctx, finished, len);
+        if (listed) {
+            rc = list_blocked(finished);
+            if (!rc && !list_.empty()) {
+                *listed = true;
+                return KGX_OK;
+            }
+        }
+        if (!rc)
+            rc = inflate(ctx, finished, len);
         *text = text_;
     } else if (joined) {
         joined_.clear();
@@ -454,6 +547,7 @@ int GzipBodyReader::inflate(kgx_ctx *ctx, bool finished, size_t *len)
         if (rc)
             return rc;
         members_ += gs.members;
+        last_members_ = gs.members;
         break;
     }
     tail_.erase(0, (size_t)consumed);

@@ -8,6 +8,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "kgx_inflate.h"
 
@@ -223,6 +224,13 @@ inline GzipBody gzip_sniff(const char *held, size_t n_held, const char *block, s
     return have < 10 && !finished ? GZ_BODY_HELD : GZ_BODY_GZIP;
 }
 
+/* a complete blocked member of a block: its deflate data at in_off of the
+ * block's compressed bytes, its text at out_off of the block's text */
+struct GzipListed {
+    uint64_t in_off, out_off;
+    uint32_t in_len, out_len, crc;
+};
+
 /* A body arriving in blocks, as text: the sniff, then either the caller's own
  * bytes (a text body; the held start and the block joined if bytes were
  * held) or the text of the block's complete gzip members, inflated on ctx
@@ -240,12 +248,41 @@ public:
      * KGX_OK with *text = null: the bytes are held, nothing to process yet;
      * else *text, *len (valid until the next call) and gzip() describe them */
     int feed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh, const char **text, size_t *len);
+    /* feed() for a caller that inflates blocked members itself, on the device
+     * into a buffer of its own (the fq handler under option "fq_body_device"):
+     * when the body is gzip and every complete member of the block is blocked,
+     * nothing is inflated -- *listed is set, list() describes the members
+     * (in_off into compressed(), out_off counting from 0) and the caller runs
+     * them in groups through inflate_listed(), then calls listed_done().  Any
+     * other block is feed()'s (a plain member: host text at `finished`). */
+    int feed_listed(kgx_ctx *ctx, const char *block, size_t n, bool finished, bool fresh, const char **text,
+                    size_t *len, bool *listed);
+    const std::vector<GzipListed> &list() const { return list_; }
+    const char *compressed() const { return tail_.data(); }
+    size_t compressed_len() const { return list_len_; } /* bytes of compressed() the listed members span */
+    /* members [first, first + count) of list(), read from d_gz (compressed()
+     * uploaded) on ctx's stream; member m's text goes to d_out + out_base +
+     * (its out_off - the first one's).  Synchronous.  A bad member is
+     * KGX_EFORMAT, named by its number in the block as feed() names it. */
+    int inflate_listed(kgx_ctx *ctx, const void *d_gz, uint32_t first, uint32_t count, void *d_out,
+                       uint64_t out_base);
+    /* the listed members are done with: their bytes leave the reader, and the
+     * body ends if the block was its last */
+    void listed_done(bool finished);
+    /* the block's members again, all on the host (a record too long for the
+     * device): the text feed() would have given */
+    int inflate_listed_on_host(kgx_ctx *ctx, bool finished, const char **text, size_t *len);
+    uint64_t last_members() const { return last_members_; } /* members the last feed() inflated to host text */
     void reset();
     GzipBody body() const { return body_; }
     bool gzip() const { return gzip_; } /* the text of the last feed() was inflated */
 
 private:
     int inflate(kgx_ctx *ctx, bool finished, size_t *len);
+    int list_blocked(bool finished);
+    std::vector<GzipListed> list_;
+    size_t list_len_ = 0;
+    uint64_t last_members_ = 0;
     GzipBody body_ = GZ_BODY_UNKNOWN; /* of the body in progress */
     bool gzip_ = false;
     std::string tail_;     /* held first bytes / compressed bytes not consumed yet */

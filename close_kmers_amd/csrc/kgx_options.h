@@ -120,6 +120,12 @@ struct CtxOptions {
      * the default stays 0 until that is repeated on a second box (DESIGN.md
      * §8.12, §12) */
     int64_t fq_parse_device = 0;
+    /* kgx_fq_process: a request's text is framed on the device part by part
+     * (kgx_fq_parse, lenient), a gzip body's blocked members are inflated into
+     * that text on the device, and the printed reads' ids come down through
+     * kgx_fq_read_ids (kguts_fq.cpp).  The output is the same
+     * bytes; the default stays 0 until a second box repeats the measurement */
+    int64_t fq_body_device = 0;
 };
 
 struct CtxOptionRow {
@@ -187,6 +193,7 @@ static const CtxOptionRow CTX_OPTION_TABLE_LATER[] = {
     {KGX_OPT(gunzip_device), 0, 1, "0 or 1", nullptr},
     {KGX_OPT(score_lean), 0, 2, "0, 1 or 2", nullptr},
     {KGX_OPT(fq_parse_device), 0, 1, "0 or 1", nullptr},
+    {KGX_OPT(fq_body_device), 0, 1, "0 or 1", nullptr},
 };
 #undef KGX_OPT
 

@@ -490,6 +490,15 @@ struct kgx_ctx {
     kgx::DevBuf fp_text, fp_map, fp_state, fp_lane, fp_cnt, fp_pre, fp_sum;
     kgx::PinnedVec<uint64_t> h_fp_sum;
     std::vector<hipEvent_t> fp_events; /* timing: upload start, parse start, parse end */
+    kgx_fq_reads fp_last{};            /* what the last parse returned (zero once its buffers are written again) */
+    /* kgx_fq_read_ids (kgx_fq_ids.hip): the chosen reads, per read its id's
+     * offset within its tile, the tiles' sums and their prefix, the ids and
+     * their offsets */
+    kgx::DevBuf fi_index, fi_local, fi_cnt, fi_pre, fi_sum, fi_ids, fi_off;
+    kgx::PinnedVec<uint32_t> h_fi_index;
+    kgx::PinnedVec<uint64_t> h_fi_off;
+    kgx::PinnedVec<char> h_fi_ids;
+    uint64_t fq_ids_fetched = 0; /* ids kgx_fq_read_ids brought down */
     /* kgx_fa_parse (kgx_fa_parse.hip): the last FASTA text's residues, sequence
      * offsets, ids and id offsets; its scratch is the fp_* above */
     kgx::DevBuf fa_res, fa_soff, fa_ids, fa_idoff;

@@ -970,12 +970,22 @@ int kgx_ctx_create(kgx_image *img, kgx_ctx **out)
         if (*p)
             fq_parse_device = *p == '1';
     }
+    /* KGX_FQ_BODY_DEVICE=0|1: the default of option "fq_body_device" for new
+     * contexts (kgx_query and kgx_server reach their handlers' contexts so) */
+    int64_t fq_body_device = CtxOptions{}.fq_body_device;
+    if (const char *p = std::getenv("KGX_FQ_BODY_DEVICE")) {
+        if (*p && std::strcmp(p, "0") && std::strcmp(p, "1"))
+            return fail(KGX_EINVAL, std::string("KGX_FQ_BODY_DEVICE: 0 (host threads) or 1 (device), not \"") + p + "\"");
+        if (*p)
+            fq_body_device = *p == '1';
+    }
     kgx_ctx *c = new kgx_ctx;
     c->img = img;
     c->probe_defer = probe_defer;
     c->opt.gunzip_device = gunzip_device;
     c->opt.score_lean = score_lean;
     c->opt.fq_parse_device = fq_parse_device;
+    c->opt.fq_body_device = fq_body_device;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -1074,6 +1084,24 @@ int kgx_ctx_set_option(kgx_ctx *c, const char *name, int64_t value)
     std::string err;
     if (ctx_option_set(c->opt, name, value, &err))
         return fail(KGX_EINVAL, err);
+    return KGX_OK;
+}
+
+int kgx_ctx_get_option(kgx_ctx *c, const char *name, int64_t *value)
+{
+    if (!c || !name || !value)
+        return fail(KGX_EINVAL, "null argument");
+    if (!ctx_option_get(c->opt, name, value))
+        return fail(KGX_EINVAL, std::string("unknown option ") + name);
+    return KGX_OK;
+}
+
+int kgx_ctx_memcpy_d2d(kgx_ctx *c, void *dst, const void *src, uint64_t n)
+{
+    if (!c || (n && (!dst || !src)))
+        return fail(KGX_EINVAL, "null argument");
+    if (n)
+        HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
     return KGX_OK;
 }
 

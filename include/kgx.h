@@ -693,8 +693,19 @@ void *kgx_ctx_stream(kgx_ctx *ctx);
  * "fq_parse_device" 0 (default) / 1: kgx_f2p_process frames a part's FASTQ
  * text with the host's strict parser / on the device (kgx_fq_parse); read when
  * a file starts; the output does not change.  KGX_FQ_PARSE_DEVICE=0|1 in the
- * environment sets the default of new contexts */
+ * environment sets the default of new contexts.
+ * "fq_body_device" 0 (default) / 1: the fq handler (kgx_fq_process) frames a
+ * request's FASTQ text on host threads / on the device (kgx_fq_parse, lenient),
+ * part by part, the unconsumed text carried in front of the next part; a gzip
+ * body's blocked members are then inflated on the device straight into the
+ * text the parser reads (kgx_gunzip_device, whatever "gunzip_device" says),
+ * and the ids of the reads it prints come down through kgx_fq_read_ids.  Read
+ * from the handler's own context when a request starts; the output bytes do
+ * not change.  KGX_FQ_BODY_DEVICE=0|1 in the environment sets
+ * the default of new contexts */
 int kgx_ctx_set_option(kgx_ctx *ctx, const char *name, int64_t value);
+/* the option's current value; KGX_EINVAL for an unknown name */
+int kgx_ctx_get_option(kgx_ctx *ctx, const char *name, int64_t *value);
 /* counters of the context since its creation: "fused_batches" / "small_batches"
  * (small host batches that took the one-launch path / the one-wait path),
  * "stream_fallbacks" (streamed batches rerun exact after a region overflow or
@@ -1083,6 +1094,15 @@ int kgx_fq_destroy(kgx_fq *fq);
 /* *text: output lines of the block, owned by fq, valid until the next call */
 int kgx_fq_process(kgx_fq *fq, const char *fastq, uint64_t n, int finished, const char **text,
                    uint64_t *text_len);
+/* counters of the handler since its creation: "device_parts" / "host_parts"
+ * (parts of text framed by kgx_fq_parse / parsed on the host: with option
+ * "fq_body_device" 1 the host parses only what a request's last complete
+ * record leaves, a record too long for the device, and a request handed over
+ * as reads), "device_members" / "host_members" (gzip members inflated into the
+ * parser's text on the device / to host text), "ids_fetched" (ids brought down
+ * by kgx_fq_read_ids), "reads" (reads looked up), "tail_bytes_max" (the longest
+ * text carried from one part to the next).  KGX_EINVAL for another name. */
+int kgx_fq_stat(kgx_fq *fq, const char *name, uint64_t *value);
 
 /* ---- reads -> six-frame protein FASTA (fastq_to_protein.cc)
  * For every read with a non-empty id, in input order, and each frame 1, 2, 3,
@@ -1169,6 +1189,24 @@ int kgx_fq_parse(kgx_ctx *ctx, const char *text, uint64_t n, uint32_t flags, kgx
 /* kgx_fq_proteins over the reads of this context's last kgx_fq_parse[_device]
  * call; KGX_EINVAL for reads that are not those */
 int kgx_fq_proteins_device(kgx_ctx *ctx, const kgx_fq_reads *reads, kgx_fq_text *out);
+
+/* ---- the ids of chosen reads of a device parse (kgx_fq_ids.hip, DESIGN.md
+ * §8.14).  reads is this context's last kgx_fq_parse[_device] result (the
+ * check kgx_fq_proteins_device makes, and that call's counts); read_index is
+ * a host array of n read indices, strictly ascending, each below
+ * reads->n_reads.  KGX_EINVAL otherwise, with nothing launched.  The chosen
+ * reads' ids are gathered on the device (a length pass, its scan, a copy in
+ * which 16 lanes move one id) and downloaded: ids[id_offsets[i],
+ * id_offsets[i + 1]) is the id of read read_index[i].  n = 0 gives zero ids
+ * (id_offsets[0] = 0) and launches nothing.  Synchronous. */
+typedef struct kgx_fq_ids { /* host views owned by ctx, valid until its next fq call */
+    uint32_t n;
+    uint64_t n_bytes;
+    const char *ids;            /* the chosen reads' id bytes, back to back */
+    const uint64_t *id_offsets; /* [n + 1], id_offsets[0] = 0 */
+} kgx_fq_ids;
+int kgx_fq_read_ids(kgx_ctx *ctx, const kgx_fq_reads *reads, const uint32_t *read_index, uint32_t n,
+                    kgx_fq_ids *out);
 
 /* ---- FASTA text -> sequences, on the device (kgx_fa_parse.hip, DESIGN.md
  * §8.13).  FastaParser::parse_char (fasta_parser.h:38-144) over text that
@@ -1516,6 +1554,9 @@ int kgx_host_free(void *p);
 int kgx_memcpy_h2d(void *dst, const void *src, uint64_t nbytes);
 int kgx_memcpy_d2h(void *dst, const void *src, uint64_t nbytes);
 int kgx_ctx_synchronize(kgx_ctx *ctx);
+/* n bytes from device memory to device memory, enqueued on ctx's stream:
+ * ordered with ctx's other work, not waited for */
+int kgx_ctx_memcpy_d2d(kgx_ctx *ctx, void *dst, const void *src, uint64_t nbytes);
 
 #ifdef __cplusplus
 }

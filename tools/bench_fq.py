@@ -12,6 +12,12 @@ handler (kgx_fq_process: H2D, the same GPU work, D2H, FamilyMapper and frame
 choice on the host, output text), with no family DB loaded.  CPU baseline:
 the oracle restatement of the same handler (oracle.FqSession) on a sample of
 the reads, one host thread.  Prints one JSON line.
+
+    python tools/bench_fq.py --body-device both [--gzip bgzf [--gzip-level 6 --gzip-level 1]]
+
+runs the handler leg alone with the option fq_body_device at 0 and at 1, the
+two alternating in one process on the same text or BGZF body, asserts equal
+outputs and writes profiles/fq_body_device_bench.json.
 """
 from __future__ import annotations
 
@@ -89,6 +95,14 @@ def main():
     ap.add_argument("--gzip", choices=("bgzf", "plain"), default=None,
                     help="also run the handler on the same text compressed (BGZF members of 65,280 bytes, or one "
                          "plain gzip member; level 6, compressed here and not timed), beside the text input")
+    ap.add_argument("--gzip-level", type=int, action="append", default=None,
+                    help="with --body-device and --gzip bgzf: a BGZF level to run (repeatable; default 6)")
+    ap.add_argument("--body-device", choices=("0", "1", "both"), default=None,
+                    help="the handler leg alone, with option fq_body_device at 0, at 1, or (both) the two "
+                         "alternating in one process: one warm-up pass each, then --reps timed passes each, on the "
+                         "same text (with --gzip bgzf: on the same compressed body); the outputs must be equal.  "
+                         "Writes profiles/fq_body_device_bench.json (--body-out)")
+    ap.add_argument("--body-out", default=os.path.join(ROOT, "profiles", "fq_body_device_bench.json"))
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a context option (kgx_ctx_set_option) on every worker context, e.g. probe_j=3")
     args = ap.parse_args()
@@ -121,6 +135,12 @@ def main():
     n, Lr = args.n_reads, args.length
     rng = np.random.default_rng(0x5EED0004)
     bases = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n * Lr, dtype=np.uint8)]
+    if args.body_device is not None:
+        body_device_legs(args, abi, image_files, img, bases)
+        for c in ctxs:
+            c.close()
+        img.close()
+        return
     d_bases, d_off = ctypes.c_void_p(), ctypes.c_void_p()
     abi.check(L.kgx_device_alloc(0, bases.nbytes, ctypes.byref(d_bases)), "alloc")
     abi.check(L.kgx_memcpy_h2d(d_bases, bases.ctypes.data, bases.nbytes), "h2d")
@@ -294,6 +314,105 @@ def main():
     for c in ctxs:
         c.close()
     img.close()
+
+
+def _fq_timing_lines(run):
+    """run() with KGX_FQ_TIMING=1 and the process's stderr captured: its "[fq]" lines"""
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as f:
+        os.environ["KGX_FQ_TIMING"] = "1"
+        os.dup2(f.fileno(), 2)
+        try:
+            run()
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            del os.environ["KGX_FQ_TIMING"]
+        f.seek(0)
+        return [ln for ln in f.read().decode(errors="replace").splitlines() if ln.startswith("[fq]")]
+
+
+def body_device_legs(args, abi, image_files, img, bases):
+    """--body-device: the handler on the same body with option fq_body_device 0
+    and 1 (KGX_FQ_BODY_DEVICE when each handler's context is created), the two
+    alternating pass by pass; per leg the reads/s of every timed pass, the
+    process's CPU seconds over them, the "[fq]" stage split of one further
+    pass, and the handler's counters."""
+    import resource
+    n, Lr = args.n_reads, args.length
+    hn = min(args.handler_reads or n, n)
+    text = fastq_text_fast(bases, Lr, 0, hn)
+    bodies = {"text": text}
+    if args.gzip == "bgzf":
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from bench_gunzip import bgzf_bytes
+        bodies = {f"bgzf_level_{lv}": bgzf_bytes(text, lv) for lv in (args.gzip_level or [6])}
+    elif args.gzip:
+        raise SystemExit("--body-device runs on text or on --gzip bgzf")
+    print(f"[bench_fq] {hn} reads of FASTQ text ({len(text) / 1e9:.2f} GB) ready", file=sys.stderr, flush=True)
+    which = ("0", "1") if args.body_device == "both" else (args.body_device,)
+    stat_names = ("device_parts", "host_parts", "device_members", "host_members", "ids_fetched", "reads",
+                  "tail_bytes_max")
+    result = {"metric": "fq handler reads/s by option fq_body_device", "unit": "reads/s", "reads": hn,
+              "read_len": Lr, "fastq_bytes": len(text), "timed_passes": args.reps, "warm_up_passes": 1,
+              "order": "the legs alternate pass by pass in one process", "bodies": {}}
+    with tempfile.TemporaryDirectory() as td:
+        image_files.write_index(os.path.join(td, "function.index"), [f"function {i}" for i in range(100000)])
+        image_files.write_index(os.path.join(td, "otu.index"), ["o"])
+        handlers = {}
+        for w in which:
+            os.environ["KGX_FQ_BODY_DEVICE"] = w  # read when the handler's context is created
+            handlers[w] = abi.FqHandler(img, td)
+        del os.environ["KGX_FQ_BODY_DEVICE"]
+        try:
+            for name, body in bodies.items():
+                legs = {w: {"ms": [], "cpu_s": 0.0} for w in which}
+                outs = {}
+                for w in which:
+                    outs[w] = handlers[w].process(body, True)  # warm (buffer growth)
+                for _ in range(args.reps):
+                    for w in which:
+                        r0 = resource.getrusage(resource.RUSAGE_SELF)
+                        t0 = time.perf_counter()
+                        out = handlers[w].process(body, True)
+                        legs[w]["ms"].append((time.perf_counter() - t0) * 1e3)
+                        r1 = resource.getrusage(resource.RUSAGE_SELF)
+                        legs[w]["cpu_s"] += (r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime)
+                        assert out == outs[w], f"fq_body_device {w}: a pass's output differs from its first"
+                for w in which:
+                    legs[w]["reads_per_s"] = [hn / (ms / 1e3) for ms in legs[w]["ms"]]
+                    legs[w]["stages"] = _fq_timing_lines(lambda: handlers[w].process(body, True))
+                    legs[w]["stats"] = {k: handlers[w].stat(k) for k in stat_names}
+                    legs[w]["output_lines"] = outs[w].count(b"\n")
+                same = len({bytes(o) for o in outs.values()}) == 1
+                assert same, f"{name}: the outputs of fq_body_device 0 and 1 differ"
+                result["bodies"][name] = {"body_bytes": len(body), "outputs_equal": same, "legs": legs}
+                print(f"[bench_fq] {name}: " + ", ".join(
+                    f"fq_body_device {w}: {min(legs[w]['ms']):.1f}-{max(legs[w]['ms']):.1f} ms" for w in which),
+                      file=sys.stderr, flush=True)
+        finally:
+            for h in handlers.values():
+                h.close()
+    if os.path.exists(args.body_out):  # a text run and a BGZF run share the file
+        with open(args.body_out) as f:
+            old = json.load(f)
+        if old.get("reads_by_body") is None:
+            old = {"reads_by_body": {}, "bodies": {}}
+    else:
+        old = {"reads_by_body": {}, "bodies": {}}
+    for name in result["bodies"]:
+        old["reads_by_body"][name] = hn
+    old["bodies"].update(result.pop("bodies"))
+    old.update(result)
+    old.pop("reads", None)
+    old.pop("fastq_bytes", None)
+    with open(args.body_out, "w") as f:
+        json.dump(old, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"metric": result["metric"], "out": os.path.relpath(args.body_out, ROOT),
+                      "bodies": {k: {w: v["legs"][w]["reads_per_s"] for w in v["legs"]}
+                                 for k, v in old["bodies"].items() if k in bodies}}), flush=True)
 
 
 def fastq_handler_prefix(out: bytes, n_reads: int) -> bytes:
