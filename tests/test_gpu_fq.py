@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from fq_restate import _CODE11, _translate_anchor  # noqa: F401
 from helpers import pack, synthetic_table
 
 pytestmark = pytest.mark.gpu
@@ -176,24 +177,6 @@ def test_fragments_of_long_and_empty_batches(gpu, oracle_lib):
         got.setdefault(int(h["read"][i]), []).append((int(h["frame"][i]), s))
     for r, dna in enumerate(reads):
         assert got.get(r, []) == oracle_lib.fq_fragments(dna), r
-
-
-_CODE11 = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
-_CLS = {c: i for i, c in enumerate("ACGT")} | {"U": 3}
-
-
-def _translate_anchor(bases: bytes, anchor: int, n: int) -> str:
-    """n residues from a fragment anchor: (first base) << 1 | reverse."""
-    a, rev = anchor >> 1, anchor & 1
-    out = []
-    for i in range(n):
-        if rev:
-            cs = [_CLS.get(chr(bases[a - 3 * i - k]).upper()) for k in range(3)]
-            cs = [None if c is None else 3 - c for c in cs]
-        else:
-            cs = [_CLS.get(chr(bases[a + 3 * i + k]).upper()) for k in range(3)]
-        out.append("X" if None in cs else _CODE11[cs[0] * 16 + cs[1] * 4 + cs[2]])
-    return "".join(out)
 
 
 def _anchor_reads(rng):
